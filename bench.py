@@ -15,7 +15,17 @@ every step traces new samples.  Inputs (scene + BVH) are resident in HBM, the
 framebuffer stays in HBM.  Steps are enqueued asynchronously (KHP_RENDER_ASYNC)
 and consecutive passes with equal parameters are fused into one wavefront
 (khp_ctx_params.fuse_frames, default 32); the timed region ends with khp_sync +
-a barrier, so every pass is complete.  `sync_steps` in the JSON line is the
+a barrier, so every pass is complete.
+
+A plain run does only that: scene + BVH, --warmup passes, the --steps timed
+passes, and the JSON line (value, ms_per_step, the timed passes' device times
+under `frame`).  --dump-outputs DIR then writes DIR/framebuffer.npy, the
+float32 running-mean frame the last timed pass left with its inf/NaN values
+written as 0, and DIR/framebuffer_nonfinite.npy, which says where those are
+(scene, seeds and sample numbers are fixed by the arguments, so two builds can
+be compared frame for frame).  Everything below runs only with --full.
+
+`sync_steps` in the JSON line is the
 same workload with a host wait after every pass (KIRK's synchronous call):
 one untimed call starts the series, then 12 calls are timed (with render-ahead
 a call renders its pass and the next three as one batch and the three later calls
@@ -28,7 +38,8 @@ Without WORLD_SIZE, `python bench.py --gpus N` starts those N ranks itself
 (torch.distributed.run as a child process, before this process touches a GPU)
 and exits with its status.
 
-The JSON line also carries:
+With --full the JSON line also carries (besides sync_steps, gui_steps,
+output_stage and, at N > 1, gather_check):
   roofline     -- the extend (closest-hit) kernel: algorithmic bytes
                   (28 B ray + 32 B per visited node + 32 B per
                   primitive test + 16 B hit, visit counts from an instrumented
@@ -85,6 +96,15 @@ def parse():
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--depth", type=int, default=5)
     ap.add_argument("--tile", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the instrumented pass and the rooflines, "
+                         "sync_steps, gui_steps, isolated, output_stage, cpu_baseline and (N > 1) the gather check; "
+                         "the options that size those legs only matter with --full")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the running-mean frame the timed passes left, as "
+                         "khp_read_framebuffer hands it to a caller (N > 1: rank 0's gathered frame), as two finite "
+                         "float32 arrays: DIR/framebuffer.npy (inf/NaN values written as 0) and "
+                         "DIR/framebuffer_nonfinite.npy (0 finite, 1 +inf, 2 -inf, 3 NaN)")
     ap.add_argument("--sync-check-steps", type=int, default=12,
                     help="passes timed with a host wait after each (the sync_steps field; 0: skip), after one "
                          "untimed call that starts the series")
@@ -365,6 +385,172 @@ def host_scene_for_oracle(sd, args, scenes):
     return scenes.build_config(name, width=args.width, height=args.height, **kw)
 
 
+DUMP_MAX_BYTES = 60_000_000   # both files together (the limit is 64 MB); a larger frame is written as a fixed, seeded sample of its pixels
+
+
+def dump_outputs(out_dir, fb):
+    """--dump-outputs: the (H, W, 3) running-mean frame a caller reads with
+    khp_read_framebuffer after the last timed pass (row 0 = bottom), as two
+    finite float32 arrays of that shape.  KIRK's arithmetic drives some values
+    to inf or NaN (a grazing Marschner hit divides by 0), and those stay in the
+    frame, so the dump carries them apart from the numbers:
+    DIR/framebuffer.npy: the frame with every non-finite value written as 0;
+    DIR/framebuffer_nonfinite.npy: 0 where the value is finite, 1 for +inf,
+    2 for -inf, 3 for NaN (any encoding).
+    A frame whose two files would exceed DUMP_MAX_BYTES (config 5's 4K) is written
+    as two (n, 3) arrays: the pixels at a sorted sample of flat indices drawn
+    from a fixed seed, the same for every run."""
+    import numpy as np
+
+    fb = np.ascontiguousarray(fb, np.float32)
+    h, w = fb.shape[:2]
+    what = {"frame": [h, w], "sampled_pixels": None}
+    per_pixel = 2 * 4 * fb.shape[-1]
+    if h * w * per_pixel > DUMP_MAX_BYTES:
+        n = DUMP_MAX_BYTES // per_pixel
+        idx = np.sort(np.random.default_rng(0x4B49524B).choice(h * w, size=n, replace=False))
+        fb = np.ascontiguousarray(fb.reshape(h * w, -1)[idx])
+        what["sampled_pixels"] = n
+    kind = np.zeros(fb.shape, np.float32)
+    kind[np.isposinf(fb)] = 1.0
+    kind[np.isneginf(fb)] = 2.0
+    kind[np.isnan(fb)] = 3.0
+    fb = np.where(kind == 0.0, fb, np.float32(0.0)).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "framebuffer.npy"), fb)
+    np.save(os.path.join(out_dir, "framebuffer_nonfinite.npy"), kind)
+    what.update(files={"framebuffer.npy": list(fb.shape), "framebuffer_nonfinite.npy": list(kind.shape)},
+                dtype="float32", bytes=int(fb.nbytes + kind.nbytes), nonfinite_values=int((kind != 0.0).sum()))
+    return what
+
+
+def kernel_figures(args, cnt, last, iso_st):
+    """--full: the traversal kernels' rooflines from the instrumented pass's exact
+    visit counts `cnt`, the timed passes' report `last` and the serial_stages
+    passes' report `iso_st` (or None).  Returns (roofline, isolated, frame): the
+    line's fields of those names (frame: the entries that need the counts)."""
+    depth = args.depth
+    ext_ms, ext_launches, busy_ms = last["extend_ms"], last["extend_launches"], last["extend_busy_ms"]
+    nfr = max(1, last["frames"])
+    # roofline of the extend kernel (this rank's launches)
+    rays = cnt["extend_rays"]
+    alg_bytes_frame = 44 * rays + 32 * (cnt["node_visits"] + cnt["prim_tests"])
+    launches_frame = max(1, cnt["extend_launches"])
+    avg_launch_ms = ext_ms / max(1, ext_launches)
+    # timed launches carry several fused passes: bytes per timed launch = the
+    # passes' algorithmic bytes / the launches they took
+    bytes_per_launch = alg_bytes_frame * nfr / max(1, ext_launches)
+    per_launch = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms > 0 else 0.0
+    achieved = (bytes_per_launch * ext_launches) / (busy_ms * 1e-3) / 1e9 if busy_ms > 0 else 0.0
+    frames_per_launch = nfr * launches_frame / max(1, ext_launches)
+    traffic = None if args.bdpt else pmc_traffic(frames_per_launch, args.config)  # profiles are of the default estimator
+    # per bounce: this run's algorithmic rate (exact visit counts, HIP-event launch
+    # times) next to the measured/algorithmic read ratio of the committed profile
+    prof_name, prof_pb = (None, None) if args.bdpt else pmc_per_bounce(args.config, frames_per_launch)
+    per_bounce_rl = []
+    for b in range(min(depth, 16)):
+        r_b = cnt["bounce_rays"][b]
+        if not r_b:
+            continue
+        alg_b = 44 * r_b + 32 * (cnt["bounce_nodes"][b] + cnt["bounce_prims"][b])
+        ms_b = last["bounce_extend_ms"][b] / nfr
+        row = {"bounce": b, "alg_GB_per_frame": round(alg_b / 1e9, 3), "ms_per_frame": round(ms_b, 3),
+               "alg_TBps": round(alg_b / (ms_b * 1e-3) / 1e12, 3) if ms_b > 0 else None}
+        pr = next((x for x in (prof_pb or []) if x["bounce"] == b), None)
+        if pr:
+            row["profile_read_over_alg"] = pr["measured_over_alg"]
+            row["profile_read_TBps"] = pr["measured_TBps"]
+        per_bounce_rl.append(row)
+    # the any-hit kernel (k_shadow alone; the finish is a separate streaming kernel)
+    sh_rays = cnt["shadow_rays"]
+    sh_bytes_frame = 32 * sh_rays + 32 * (cnt["shadow_node_visits"] + cnt["shadow_prim_tests"])
+    sh_ms = last["shadow_ms"] - last["shadow_finish_ms"]
+    sh_launches = max(1, last["shadow_launches"])
+    sh_bytes_per_launch = sh_bytes_frame * nfr / sh_launches
+    sh_avg_ms = sh_ms / sh_launches
+    sh_achieved = sh_bytes_per_launch / (sh_avg_ms * 1e-3) / 1e9 if sh_avg_ms > 0 else 0.0
+    isolated = None
+    if iso_st is not None:
+        nfi = max(1, iso_st["frames"])
+        e_ms, s_ms = iso_st["extend_ms"], iso_st["shadow_ms"] - iso_st["shadow_finish_ms"]
+
+        def _rl(bytes_frame, ms, launches):
+            a = bytes_frame * nfi / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+            return {"ms_per_frame": round(ms / nfi, 3), "launches": launches, "achieved": round(a, 1),
+                    "frac": round(a / HBM_PEAK_GBPS, 4)}
+        isolated = {
+            "frames": nfi, "def": "the same fused progressive passes with khp_ctx_params.serial_stages = 1 "
+                                  "(one stream: no kernel overlaps another); algorithmic bytes / kernel time",
+            "device_ms_per_frame": round(iso_st["render_ms"] / nfi, 3),
+            "k_extend": _rl(alg_bytes_frame, e_ms, iso_st["extend_launches"]),
+            "k_shadow": _rl(sh_bytes_frame, s_ms, iso_st["shadow_launches"]),
+            "k_shade_ms_per_frame": round(iso_st["shade_ms"] / nfi, 3),
+            "k_shadow_finish_ms_per_frame": round(iso_st["shadow_finish_ms"] / nfi, 3),
+        }
+        isolated["k_shadow"]["records_per_s"] = round(
+            (cnt["shadow_node_visits"] + cnt["shadow_prim_tests"]) * nfi / max(1e-9, s_ms * 1e-3), 1)
+        isolated["k_extend"]["records_per_s"] = round(
+            (cnt["node_visits"] + cnt["prim_tests"]) * nfi / max(1e-9, e_ms * 1e-3), 1)
+    roofline = {
+        "bound": "hbm",
+        "kernel": "k_extend (closest-hit traversal: bounce-0, 64-B and two-level instances together)",
+        "achieved": round(achieved, 1),
+        "peak": HBM_PEAK_GBPS,
+        "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBPS, 4),
+        "traffic": traffic,
+        "bytes_per_launch": int(bytes_per_launch),
+        "avg_launch_ms": round(avg_launch_ms, 4),
+        "achieved_per_launch": round(per_launch, 1),
+        "frames_per_launch": round(frames_per_launch, 3),
+        "alg_bytes_per_frame": int(alg_bytes_frame),
+        "extend_busy_ms_per_frame": round(busy_ms / nfr, 3),
+        "achieved_def": "algorithmic bytes of all timed k_extend launches / union of their HIP-event "
+                        "intervals (= bytes per launch / avg launch duration when launches do not overlap)",
+        "per_ray": {"nodes": round(cnt["node_visits"] / max(1, rays), 2),
+                    "prims": round(cnt["prim_tests"] / max(1, rays), 2)},
+        "per_bounce": per_bounce_rl,
+        "per_bounce_def": "alg = SURVEY §8(d) bytes of the bounce's exact visit counts; ms = the bounce's "
+                          "k_extend launches (HIP events) per frame; profile_read_* = 2 x FETCH_SIZE of "
+                          f"the bounce's launches in {prof_name} (L2 misses, Infinity-Cache hits included)",
+        "shadow": {
+            "kernel": "k_shadow (any-hit BVH2 traversal)",
+            "achieved_def": "algorithmic bytes per launch / average launch duration of the overlapped "
+                            "launches, which share the chip with the next bounce's k_extend; the "
+                            "kernel's own rate is isolated.k_shadow",
+            "achieved": round(sh_achieved, 1), "frac": round(sh_achieved / HBM_PEAK_GBPS, 4),
+            "bytes_per_launch": int(sh_bytes_per_launch), "avg_launch_ms": round(sh_avg_ms, 4),
+            "alg_bytes_per_frame": int(sh_bytes_frame),
+            "per_ray": {"nodes": round(cnt["shadow_node_visits"] / max(1, sh_rays), 2),
+                        "prims": round(cnt["shadow_prim_tests"] / max(1, sh_rays), 2)},
+            "records_per_s": round((cnt["shadow_node_visits"] + cnt["shadow_prim_tests"]) * nfr /
+                                   max(1e-9, sh_ms * 1e-3), 1),
+        },
+    }
+    frame = {
+        "extend_rays": rays, "shadow_rays": sh_rays,
+        "extend_records_per_s": round((cnt["node_visits"] + cnt["prim_tests"]) * nfr / max(1e-9, ext_ms * 1e-3), 1),
+        "stack_spills_per_ray": round(cnt["stack_spills"] / max(1, rays + sh_rays), 4),
+        "pruned_pops_per_ray": round(cnt["extend_pruned_pops"] / max(1, rays), 3),
+        "shadow_pruned_pops_per_ray": round(cnt["shadow_pruned_pops"] / max(1, sh_rays), 3),
+        "per_bounce": [
+            {"bounce": b, "rays": cnt["bounce_rays"][b],
+             "nodes_per_ray": round(cnt["bounce_nodes"][b] / max(1, cnt["bounce_rays"][b]), 2),
+             "prims_per_ray": round(cnt["bounce_prims"][b] / max(1, cnt["bounce_rays"][b]), 2),
+             "extend_ms": round(last["bounce_extend_ms"][b] / nfr, 3),
+             "shadow_rays": cnt["bounce_shadow_rays"][b],
+             "shadow_nodes_per_ray": round(cnt["bounce_shadow_nodes"][b] / max(1, cnt["bounce_shadow_rays"][b]), 2),
+             "shadow_prims_per_ray": round(cnt["bounce_shadow_prims"][b] / max(1, cnt["bounce_shadow_rays"][b]), 2),
+             "shadow_ms": round(last["bounce_shadow_ms"][b] / nfr, 3),
+             "wave_iters": cnt["bounce_wave_iters"][b],
+             "lane_use": round(cnt["bounce_lanes_busy"][b] / max(1, 64 * cnt["bounce_wave_iters"][b]), 3),
+             "shadow_lane_use": round(cnt["bounce_shadow_lanes_busy"][b] /
+                                      max(1, 64 * cnt["bounce_shadow_wave_iters"][b]), 3)}
+            for b in range(min(depth, 16))],
+    }
+    return roofline, isolated, frame
+
+
 def main():
     args = parse()
     sys.path.insert(0, HERE)
@@ -425,9 +611,11 @@ def main():
     for _ in range(args.warmup):
         step()
     frame.sync()
-    # one instrumented pass (outside the timed region): exact visit counts
-    step(stats=True)
-    cnt = ctx.stats()
+    # --full: one instrumented pass (outside the timed region): exact visit counts
+    cnt = None
+    if args.full:
+        step(stats=True)
+        cnt = ctx.stats()
 
     frame.sync()
     frame.barrier()
@@ -438,14 +626,16 @@ def main():
     frame.barrier()
     elapsed = frame.max_over_ranks(time.perf_counter() - t0)
     last = ctx.stats()   # sums over the timed passes (khp_sync report)
-    ext_ms, ext_launches, busy_ms = last["extend_ms"], last["extend_launches"], last["extend_busy_ms"]
     nfr = max(1, last["frames"])
     samples_per_step = W * H * spp
     value = args.steps * samples_per_step / elapsed / 1e6
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, ctx.read_framebuffer(W, H))
 
     # the same workload with a host wait after every pass (no fusion, no overlap)
     sync_line = None
-    if args.sync_check_steps > 0:
+    if args.full and args.sync_check_steps > 0:
         step(async_=False)   # the series' first call (untimed): render-ahead starts with the second
         frame.sync()
         frame.barrier()
@@ -473,7 +663,7 @@ def main():
     # render() call adds ONE sample to every pixel synchronously and the viewer
     # then reads the 8-bit texture (drawTexture -> Texture::setPixel)
     gui_line = None
-    if args.gui_steps > 0 and rank == 0 and world == 1:
+    if args.full and args.gui_steps > 0 and rank == 0 and world == 1:
         for g in range(2):   # the series' first calls (render-ahead fills up), untimed
             ctx.render(W, H, 1, depth, first_sample=k * spp + g, readback=False)
             ctx.read_rgba8(W, H)
@@ -522,7 +712,7 @@ def main():
     # isolated per-kernel rooflines (k_shadow's overlapped launch time above also
     # counts the co-running k_extend's share of the chip)
     iso_st = None
-    if args.iso_steps > 0:
+    if args.full and args.iso_steps > 0:
         old_prm = ctx.set_params(serial_stages=1)
         for _ in range(args.iso_steps):
             step()
@@ -530,68 +720,10 @@ def main():
         iso_st = ctx.stats()
         ctx.set_params(**old_prm)
 
-    # roofline of the extend kernel (this rank's launches)
-    rays = cnt["extend_rays"]
-    alg_bytes_frame = 44 * rays + 32 * (cnt["node_visits"] + cnt["prim_tests"])
-    launches_frame = max(1, cnt["extend_launches"])
-    avg_launch_ms = ext_ms / max(1, ext_launches)
-    # timed launches carry several fused passes: bytes per timed launch = the
-    # passes' algorithmic bytes / the launches they took
-    bytes_per_launch = alg_bytes_frame * nfr / max(1, ext_launches)
-    per_launch = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9 if avg_launch_ms > 0 else 0.0
-    achieved = (bytes_per_launch * ext_launches) / (busy_ms * 1e-3) / 1e9 if busy_ms > 0 else 0.0
-    frames_per_launch = nfr * launches_frame / max(1, ext_launches)
-    traffic = None if args.bdpt else pmc_traffic(frames_per_launch, args.config)  # profiles are of the default estimator
-    # per bounce: this run's algorithmic rate (exact visit counts, HIP-event launch
-    # times) next to the measured/algorithmic read ratio of the committed profile
-    prof_name, prof_pb = (None, None) if args.bdpt else pmc_per_bounce(args.config, frames_per_launch)
-    per_bounce_rl = []
-    for b in range(min(depth, 16)):
-        r_b = cnt["bounce_rays"][b]
-        if not r_b:
-            continue
-        alg_b = 44 * r_b + 32 * (cnt["bounce_nodes"][b] + cnt["bounce_prims"][b])
-        ms_b = last["bounce_extend_ms"][b] / nfr
-        row = {"bounce": b, "alg_GB_per_frame": round(alg_b / 1e9, 3), "ms_per_frame": round(ms_b, 3),
-               "alg_TBps": round(alg_b / (ms_b * 1e-3) / 1e12, 3) if ms_b > 0 else None}
-        pr = next((x for x in (prof_pb or []) if x["bounce"] == b), None)
-        if pr:
-            row["profile_read_over_alg"] = pr["measured_over_alg"]
-            row["profile_read_TBps"] = pr["measured_TBps"]
-        per_bounce_rl.append(row)
-    # the any-hit kernel (k_shadow alone; the finish is a separate streaming kernel)
-    sh_rays = cnt["shadow_rays"]
-    sh_bytes_frame = 32 * sh_rays + 32 * (cnt["shadow_node_visits"] + cnt["shadow_prim_tests"])
-    sh_ms = last["shadow_ms"] - last["shadow_finish_ms"]
-    sh_launches = max(1, last["shadow_launches"])
-    sh_bytes_per_launch = sh_bytes_frame * nfr / sh_launches
-    sh_avg_ms = sh_ms / sh_launches
-    sh_achieved = sh_bytes_per_launch / (sh_avg_ms * 1e-3) / 1e9 if sh_avg_ms > 0 else 0.0
-    isolated = None
-    if iso_st is not None:
-        nfi = max(1, iso_st["frames"])
-        e_ms, s_ms = iso_st["extend_ms"], iso_st["shadow_ms"] - iso_st["shadow_finish_ms"]
-
-        def _rl(bytes_frame, ms, launches):
-            a = bytes_frame * nfi / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-            return {"ms_per_frame": round(ms / nfi, 3), "launches": launches, "achieved": round(a, 1),
-                    "frac": round(a / HBM_PEAK_GBPS, 4)}
-        isolated = {
-            "frames": nfi, "def": "the same fused progressive passes with khp_ctx_params.serial_stages = 1 "
-                                  "(one stream: no kernel overlaps another); algorithmic bytes / kernel time",
-            "device_ms_per_frame": round(iso_st["render_ms"] / nfi, 3),
-            "k_extend": _rl(alg_bytes_frame, e_ms, iso_st["extend_launches"]),
-            "k_shadow": _rl(sh_bytes_frame, s_ms, iso_st["shadow_launches"]),
-            "k_shade_ms_per_frame": round(iso_st["shade_ms"] / nfi, 3),
-            "k_shadow_finish_ms_per_frame": round(iso_st["shadow_finish_ms"] / nfi, 3),
-        }
-        isolated["k_shadow"]["records_per_s"] = round(
-            (cnt["shadow_node_visits"] + cnt["shadow_prim_tests"]) * nfi / max(1e-9, s_ms * 1e-3), 1)
-        isolated["k_extend"]["records_per_s"] = round(
-            (cnt["node_visits"] + cnt["prim_tests"]) * nfi / max(1e-9, e_ms * 1e-3), 1)
-    # N > 1: rank 0's gathered frame against the untiled frame of the same passes
+    roofline, isolated, frame_counts = kernel_figures(args, cnt, last, iso_st) if args.full else (None, None, {})
+    # --full, N > 1: rank 0's gathered frame against the untiled frame of the same passes
     check = None
-    if world > 1 and not args.no_gather_check:
+    if args.full and world > 1 and not args.no_gather_check:
         frame.sync()
         if rank == 0:
             check = gather_check(args, k, ctx.read_framebuffer(W, H), scenes)
@@ -623,73 +755,23 @@ def main():
         "sync_steps": sync_line,
         "gui_steps": gui_line,
         "isolated": isolated,
-        "roofline": {
-            "bound": "hbm",
-            "kernel": "k_extend (closest-hit traversal: bounce-0, 64-B and two-level instances together)",
-            "achieved": round(achieved, 1),
-            "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBPS, 4),
-            "traffic": traffic,
-            "bytes_per_launch": int(bytes_per_launch),
-            "avg_launch_ms": round(avg_launch_ms, 4),
-            "achieved_per_launch": round(per_launch, 1),
-            "frames_per_launch": round(frames_per_launch, 3),
-            "alg_bytes_per_frame": int(alg_bytes_frame),
-            "extend_busy_ms_per_frame": round(busy_ms / nfr, 3),
-            "achieved_def": "algorithmic bytes of all timed k_extend launches / union of their HIP-event "
-                            "intervals (= bytes per launch / avg launch duration when launches do not overlap)",
-            "per_ray": {"nodes": round(cnt["node_visits"] / max(1, rays), 2),
-                        "prims": round(cnt["prim_tests"] / max(1, rays), 2)},
-            "per_bounce": per_bounce_rl,
-            "per_bounce_def": "alg = SURVEY §8(d) bytes of the bounce's exact visit counts; ms = the bounce's "
-                              "k_extend launches (HIP events) per frame; profile_read_* = 2 x FETCH_SIZE of "
-                              f"the bounce's launches in {prof_name} (L2 misses, Infinity-Cache hits included)",
-            "shadow": {
-                "kernel": "k_shadow (any-hit BVH2 traversal)",
-                "achieved_def": "algorithmic bytes per launch / average launch duration of the overlapped "
-                                "launches, which share the chip with the next bounce's k_extend; the "
-                                "kernel's own rate is isolated.k_shadow",
-                "achieved": round(sh_achieved, 1), "frac": round(sh_achieved / HBM_PEAK_GBPS, 4),
-                "bytes_per_launch": int(sh_bytes_per_launch), "avg_launch_ms": round(sh_avg_ms, 4),
-                "alg_bytes_per_frame": int(sh_bytes_frame),
-                "per_ray": {"nodes": round(cnt["shadow_node_visits"] / max(1, sh_rays), 2),
-                            "prims": round(cnt["shadow_prim_tests"] / max(1, sh_rays), 2)},
-                "records_per_s": round((cnt["shadow_node_visits"] + cnt["shadow_prim_tests"]) * nfr /
-                                       max(1e-9, sh_ms * 1e-3), 1),
-            },
-        },
+        "roofline": roofline,
         "frame": {
-            "extend_rays": rays, "shadow_rays": sh_rays,
             "extend_ms": round(last["extend_ms"] / nfr, 3), "shade_ms": round(last["shade_ms"] / nfr, 3),
             "shadow_ms": round(last["shadow_ms"] / nfr, 3),
             "shadow_finish_ms": round(last["shadow_finish_ms"] / nfr, 3),
             "other_ms": round(last["other_ms"] / nfr, 3),
             "device_ms": round(last["render_ms"] / nfr, 3),
-            "extend_records_per_s": round((cnt["node_visits"] + cnt["prim_tests"]) * nfr / max(1e-9, ext_ms * 1e-3), 1),
-            "stack_spills_per_ray": round(cnt["stack_spills"] / max(1, rays + sh_rays), 4),
-            "pruned_pops_per_ray": round(cnt["extend_pruned_pops"] / max(1, rays), 3),
-            "shadow_pruned_pops_per_ray": round(cnt["shadow_pruned_pops"] / max(1, sh_rays), 3),
             "fused_frames": min(args.steps, params["fuse_frames"]), "params": params,
             "build_s": round(build_s, 3),
             "setup": setup,
-            "per_bounce": [
-                {"bounce": b, "rays": cnt["bounce_rays"][b],
-                 "nodes_per_ray": round(cnt["bounce_nodes"][b] / max(1, cnt["bounce_rays"][b]), 2),
-                 "prims_per_ray": round(cnt["bounce_prims"][b] / max(1, cnt["bounce_rays"][b]), 2),
-                 "extend_ms": round(last["bounce_extend_ms"][b] / nfr, 3),
-                 "shadow_rays": cnt["bounce_shadow_rays"][b],
-                 "shadow_nodes_per_ray": round(cnt["bounce_shadow_nodes"][b] / max(1, cnt["bounce_shadow_rays"][b]), 2),
-                 "shadow_prims_per_ray": round(cnt["bounce_shadow_prims"][b] / max(1, cnt["bounce_shadow_rays"][b]), 2),
-                 "shadow_ms": round(last["bounce_shadow_ms"][b] / nfr, 3),
-                 "wave_iters": cnt["bounce_wave_iters"][b],
-                 "lane_use": round(cnt["bounce_lanes_busy"][b] / max(1, 64 * cnt["bounce_wave_iters"][b]), 3),
-                 "shadow_lane_use": round(cnt["bounce_shadow_lanes_busy"][b] /
-                                          max(1, 64 * cnt["bounce_shadow_wave_iters"][b]), 3)}
-                for b in range(min(depth, 16))],
+            **frame_counts,
         },
+        "full": args.full,
     }
-    if rank == 0:
+    if dumped is not None:
+        out["dump_outputs"] = dumped
+    if args.full and rank == 0:
         # output stage, outside the timed region: the device
         # 8-bit conversion and Tonemapper::map, wall time including the D2H copy of
         # W*H*4 bytes (kernel durations: profiles/*_kernel_stats.csv)
@@ -704,7 +786,7 @@ def main():
             o[key] = round((time.perf_counter() - t1) / 5 * 1e3, 3)
         o["bytes_per_pixel"] = {"rgba8": 16, "tonemap": 40}
         out["output_stage"] = o
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(host_scene_for_oracle(sd, args, scenes), args, args.cpu_seconds)
         except Exception as e:  # reported, never silently replaced

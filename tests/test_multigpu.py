@@ -50,7 +50,7 @@ def test_rccl_gather_assembles_the_single_gpu_frame(tmp_path, world, W, H):
 def test_bench_launches_its_own_ranks():
     if _n_gpus() < 2:
         pytest.skip(f"needs 2 GPUs, this box has {_n_gpus()}")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "1", "--steps",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--config", "1", "--steps",
                           "4", "--warmup", "2", "--sync-check-steps", "1", "--no-cpu-baseline"], check=True,
                          timeout=300, capture_output=True, text=True).stdout
     line = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
@@ -455,7 +455,8 @@ def test_bench_two_ranks_on_one_gpu():
     passes, max-over-ranks timing and rank 0's gather check on a second real
     context.  Only the transport is replaced (RCCL refuses two ranks on one GPU):
     tests/_bench_hip_gloo.py moves the product plan's pixels over gloo."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "1", "--width", "64",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--config", "1", "--width",
+                          "64",
                           "--height", "48", "--spp", "2", "--tile", "16", "--steps", "3", "--warmup", "1",
                           "--sync-check-steps", "1", "--iso-steps", "1", "--gui-steps", "0", "--no-cpu-baseline",
                           "--ctx-factory", "tests/_bench_hip_gloo.py:HipGlooCtx", "--launch-timeout", "200"],

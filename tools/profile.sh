@@ -6,12 +6,12 @@ set -e
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=${1:-r01}; shift || true
 PASSES=${@:-trace fetch write sq}
-OUT=$R/gpurun_out/prof_$TAG
+OUT=$R/${OUT_DIR:-bench_out}/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 KREGEX=${KREGEX:-k_extend|k_shadow}  # kernels the PMC passes count
 STEPS=${STEPS:-32}  # the default bench line's 32 fused passes: 4 chunks of 8 frames, as in the timed region
-B="python3 $R/bench.py --no-cpu-baseline --sync-check-steps 0 --iso-steps 0 --gui-steps 0 --config ${CFG:-metric}"  # every k_extend launch of the run then carries the same fused frames
+B="python3 $R/bench.py --full --no-cpu-baseline --sync-check-steps 0 --iso-steps 0 --gui-steps 0 --config ${CFG:-metric}"  # every k_extend launch of the run then carries the same fused frames
 for p in $PASSES; do
   case $p in
     list)  timeout -k 10 120 rocprofv3 -L > $OUT/counters.txt 2>&1 || true ;;
