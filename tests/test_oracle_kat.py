@@ -468,6 +468,104 @@ def test_equal_t_within_a_leaf_takes_the_later_candidate(n_extra):
     assert abs(t[0] - 3.0) < 1e-6 and obj[0] == later
 
 
+# A ray across the joint of two collinear cylinders (0,0,0)->(0,1,0)->(0,2,0), r = 0.1, in the
+# plane z = 0: it enters the common infinite cylinder at x = -0.1, y = 0.95 (t1 = 0.5 sqrt 5, on
+# the lower cylinder) and leaves it at x = 0.1, y = 1.05 (t2 = 0.6 sqrt 5, on the upper one).
+# Both cylinders get the same frame (u, v, w) = (x, y, z), the same P.x, P.z and slope 0, hence
+# the same float32 roots bit for bit.
+JOINT_ORIGIN = (-1.1, 0.45, 0.0)
+JOINT_DIR = tuple((np.float32([2.0, 1.0, 0.0]) / np.sqrt(np.float32(5.0))).tolist())
+JOINT_T1, JOINT_T2 = 0.5 * np.sqrt(5.0), 0.6 * np.sqrt(5.0)
+JOINT_BETWEEN_ROOTS = 1.25
+
+
+def _joint_cylinders(lower_first, only_upper=False):
+    sd = S.SceneData(name="joint")
+    m = sd.add_material(S.material())
+    lower, upper = ([0, 0, 0, 0.1], [0, 1, 0, 0.1]), ([0, 1, 0, 0.1], [0, 2, 0, 0.1])
+    cones = [upper] if only_upper else ([lower, upper] if lower_first else [upper, lower])
+    sd.add_cones(np.float32([c[0] for c in cones]), np.float32([c[1] for c in cones]), m)
+    sd.cam = S.camera((0, 0, 5), (0, 0, -1), width=8, height=8)
+    return sd
+
+
+@pytest.mark.parametrize("lower_first", [True, False], ids=["lower_first", "upper_first"])
+def test_second_root_overwrites_a_nearer_hit(lower_first):
+    """Appendix A.16 (Cylinder.cpp:132-153, Container.cpp:13-25): with two roots
+    >= cRayEpsilon, Cylinder::closestIntersection tries t1 and, if t1 lies outside
+    the cone's height window, accepts t2 inside it with no t2 <= tMax check; the
+    leaf loop then lets this later candidate overwrite the hit found before it.
+    Two collinear cylinders share the one leaf of their scene; the ray crosses
+    the joint.  The float64 truth is the lower cylinder at t1.  KIRK returns the
+    candidate listed later in the leaf: the lower cylinder at t1 when it is the
+    later one, otherwise the upper cylinder at its far root t2."""
+    import _geomref as G
+    sd = _joint_cylinders(lower_first)
+    o = oracle_ffi.Oracle(sd)
+    boxes, first, count, ids, depth = o.bvh()
+    assert count.tolist() == [2]                       # one leaf (KIRK never splits two objects)
+    members = ids[first[0]:first[0] + 2].tolist()
+    assert members == [0, 1]                           # in insertion order
+    lower = 0 if lower_first else 1
+    t64, obj64 = G.brute_force(sd, [JOINT_ORIGIN], [JOINT_DIR])
+    assert obj64[0] == lower and abs(t64[0] - JOINT_T1) < 1e-6
+    t, obj, *_ = o.trace_closest([JOINT_ORIGIN], [JOINT_DIR])
+    assert obj[0] == members[-1]
+    assert abs(t[0] - (JOINT_T1 if members[-1] == lower else JOINT_T2)) < 1e-5
+    assert (obj[0] != obj64[0]) == lower_first
+
+
+def test_any_hit_accepts_a_second_root_beyond_tmax():
+    """Appendix A.16, the any-hit form (Cylinder.cpp:158-228): Cylinder::isIntersection
+    has the same fall-through.  The upper cylinder alone: its near root t1 (below the
+    base plane) is no hit, its only hit is t2.  With t1 < tMax < t2 nothing is hit
+    within tMax, yet KIRK reports a hit; with tMax < t1 it reports none."""
+    import _geomref as G
+    sd = _joint_cylinders(True, only_upper=True)
+    o = oracle_ffi.Oracle(sd)
+    t64, obj64 = G.brute_force(sd, [JOINT_ORIGIN], [JOINT_DIR])
+    assert obj64[0] == 0 and abs(t64[0] - JOINT_T2) < 1e-6 and JOINT_T1 < JOINT_BETWEEN_ROOTS < t64[0]
+    t, obj, *_ = o.trace_closest([JOINT_ORIGIN], [JOINT_DIR])
+    assert obj[0] == 0 and abs(t[0] - JOINT_T2) < 1e-5
+    assert o.trace_any([JOINT_ORIGIN], [JOINT_DIR], [JOINT_BETWEEN_ROOTS])[0]
+    assert not o.trace_any([JOINT_ORIGIN], [JOINT_DIR], [1.0])[0]
+    assert o.trace_any([JOINT_ORIGIN], [JOINT_DIR], [1.5])[0]
+
+
+PRUNE_ORIGIN, PRUNE_DIR = (0.0, -0.3, 3.0), (0.0, 0.0, -1.0)
+
+
+def _entered_at_the_best_scene():
+    """Two leaves of two triangles each.  The ray hits A (z = 0) at t = 3 exactly;
+    the other leaf's box, B's top z = -1e-4 plus the ctor's 1e-4, has its near
+    face at z = 0 exactly, so the ray enters it at tmin = 3 = the current best."""
+    zb = np.float32(-1e-4)
+    v = np.float32([[[-1, -1, 0], [1, -1, 0], [0, 1, 0]],                    # A
+                    [[1.5, 1.5, 0.5], [1.6, 1.5, 0.5], [1.5, 1.6, 0.5]],     # beside A, off the ray
+                    [[-3, -2, zb], [1, -1, zb], [-0.5, 4, -20]],             # B, under the ray behind A
+                    [[-2, 2, -8], [-1.9, 2, -8], [-2, 2.1, -8]]])            # beside B's centroid, off the ray
+    sd = S.SceneData(name="entered_at_the_best")
+    sd.add_triangles(v, np.broadcast_to(np.float32([0, 0, 1]), v.shape).copy(), sd.add_material(S.material()))
+    sd.cam = S.camera((0, 0, 5), (0, 0, -1), width=8, height=8)
+    return sd
+
+
+def test_node_entered_at_the_current_best_is_still_visited():
+    """CPU_BVH.cpp:148-152: a node is skipped only if tmin > the best lambda, so a
+    node entered exactly at the best hit is still visited and its candidates
+    tested.  The answer cannot differ (a leaf replaces the hit only at t < best,
+    and nothing inside a box is nearer than the box), so the visit counts pin it:
+    root and both leaves, all four candidates."""
+    o = oracle_ffi.Oracle(_entered_at_the_best_scene())
+    boxes, first, count, ids, depth = o.bvh()
+    assert count.tolist() == [0, 2, 2]
+    leaf_b = 1 if 2 in ids[first[1]:first[1] + 2] else 2
+    assert sorted(ids[first[leaf_b]:first[leaf_b] + 2].tolist()) == [2, 3] and boxes[leaf_b, 5] == 0.0
+    t, obj, uv, nodes, prims = o.trace_closest([PRUNE_ORIGIN], [PRUNE_DIR])
+    assert obj[0] == 0 and t[0] == np.float32(3.0)
+    assert (nodes, prims) == (3, 4)
+
+
 def _mirror_scene():
     sd = S.SceneData(name="mirror")
     m = sd.add_material(S.material("SpecularReflectionBSDF", specular=(0.5, 0.25, 1.0)))
