@@ -96,6 +96,12 @@ std::string device_flatten(const khp_scene* s, bool device_ptrs, uint32_t n_mate
 std::string device_gen_hairball(uint32_t n, uint32_t verts, const float center[3], float ball_r, float root_r,
                                 uint32_t seed, float* d_base_r0, float* d_apex_r1, hipStream_t st);
 
+// khp_gen_fur + khp_fibers_to_cones on the device (kirk_hip.h: khp_gen_fur_device);
+// the mesh and the outputs are device arrays.  Errors starting "EINVAL:" are input errors.
+std::string device_gen_fur(const khp_fur_params* p, uint32_t n_tris, const float* d_tri_v, const float* d_tri_n,
+                           uint64_t capacity_cones, float* d_base_r0, float* d_apex_r1, uint64_t* n_cones,
+                           hipStream_t st);
+
 // khp_gen_hairball followed by khp_fibers_to_triangles, on the device.
 std::string device_gen_hairball_tris(uint32_t n, uint32_t verts, const float center[3], float ball_r, float root_r,
                                      uint32_t seed, uint32_t res, float* d_v, float* d_n, float* d_frame,

@@ -1,9 +1,10 @@
 // flatten.hip -- CPU::Scene::flattenNode's per-object work on the device
 // (SURVEY §8(f)2): the Triangle / Cylinder ctor state of every object, and the
-// seeded hairball (Mesh::addFurToFaces recurrence + the fiber -> cone rule of
-// CPU_Scene.cpp:121-144) generated straight into HBM.  The arithmetic is
+// seeded hairball and the fur of a triangle mesh (Mesh::addFurToFaces + the
+// fiber -> cone rule of CPU_Scene.cpp:121-144) generated straight into HBM.  The arithmetic is
 // objects.h, the same source the host flatten (scene.cpp) runs.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 
 #include <cmath>
 #include <string>
@@ -106,7 +107,62 @@ __global__ void k_gen_hairball_tris(uint32_t n, uint32_t verts, float cx, float 
     fiber_tube_triangle(P, R, r / per_seg, res, r % per_seg, ov + 9 * t, on + 9 * t, of + 9 * t);
 }
 
-#define FLCHK(expr)                                                                  \
+// ---- fur on a mesh (khp_gen_fur + khp_fibers_to_cones) --------------------------
+// Density mode, one face per thread: its fibre count (64-bit, the scan's type).
+// err[0] bit 0 / err[1] = the first face whose count would reach 65,536.
+__global__ void __launch_bounds__(256)
+k_fur_count(const float* __restrict__ tv, uint32_t n_tris, float density, uint32_t key0, uint64_t* cnt,
+            uint32_t* err) {
+    const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_tris) return;
+    const float* v = tv + 9 * (size_t)f;
+    uint32_t c = fur_face_count(ld3(v), ld3(v + 3), ld3(v + 6), density, fur_face_key(key0, f));
+    if (c == FUR_COUNT_BAD) {
+        atomicOr(err, 1u);
+        atomicMin(err + 1, f);
+        c = 0;
+    }
+    cnt[f] = c;
+}
+
+// One fibre per thread (per-face counts vary by orders of magnitude in density
+// mode; no lane waits behind a large face).  The strand is streamed: cone c
+// needs vertices c and c + 1 only, so nothing but the last vertex is kept.
+// first: exclusive prefix of the face counts [n_tris + 1], or null (per_face each).
+__global__ void __launch_bounds__(256)
+k_gen_fur(khp_fur_params p, uint32_t key0, uint32_t n_tris, uint32_t n_fibers, uint32_t per_face,
+          const uint64_t* __restrict__ first, const float* __restrict__ tv, const float* __restrict__ tn, LnTable lnt,
+          float4* base_r0, float4* apex_r1) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_fibers) return;
+    uint32_t f, j;
+    if (first) {  // the face with first[f] <= t < first[f + 1]; first[0] = 0, first[n_tris] = n_fibers > t
+        uint32_t lo = 0, hi = n_tris;
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (first[mid] <= t) lo = mid;
+            else hi = mid;
+        }
+        f = lo;
+        j = t - (uint32_t)first[lo];
+    } else {
+        f = t / per_face;
+        j = t % per_face;
+    }
+    Strand s = fur_strand_begin(p, key0, f, j, tv + 9 * (size_t)f, tn ? tn + 9 * (size_t)f : nullptr);
+    const size_t k0 = (size_t)t * (p.verts - 1);
+    for (uint32_t c = 0; c + 1 < p.verts; ++c) {
+        const v3 b = s.pos;
+        const float br = s.radius;
+        strand_next(s, c + 1, lnt.v);
+        float ob[4], oa[4];
+        fiber_segment_at(b, s.pos, br, s.radius, c, ob, oa);
+        base_r0[k0 + c] = make_float4(ob[0], ob[1], ob[2], ob[3]);
+        apex_r1[k0 + c] = make_float4(oa[0], oa[1], oa[2], oa[3]);
+    }
+}
+
+#define FLCHK(expr)                                                                 \
     do {                                                                             \
         hipError_t e_ = (expr);                                                      \
         if (e_ != hipSuccess) return std::string(#expr) + ": " + hipGetErrorString(e_); \
@@ -227,6 +283,63 @@ std::string device_gen_hairball(uint32_t n, uint32_t verts, const float center[3
                            center[2], ball_r, root_r, key0, t, (float4*)d_base_r0, (float4*)d_apex_r1);
     FLCHK(hipGetLastError());
     FLCHK(hipStreamSynchronize(st));
+    return std::string();
+}
+
+std::string device_gen_fur(const khp_fur_params* p, uint32_t n_tris, const float* d_tri_v, const float* d_tri_n,
+                           uint64_t capacity_cones, float* d_base_r0, float* d_apex_r1, uint64_t* n_cones,
+                           hipStream_t st) {
+    using namespace fl;
+    std::string perr = fur_params_error(p);
+    if (!perr.empty()) return "EINVAL:" + perr;
+    if (!n_cones) return "EINVAL:fur: n_cones is null";
+    const bool dens = p->density > 0.0f;
+    if (n_tris && !d_tri_v && (dens || d_base_r0)) return "EINVAL:fur: d_tri_v is null";
+    if (n_tris >= 0x7fffffffu) return "EINVAL:fur: more than 2^31 - 2 faces";  // the scan counts in int
+    const uint32_t key0 = fur_key0(p->seed);
+    DevMem cnt, first, err, tmp;
+    uint64_t n_fibers = (uint64_t)n_tris * p->fibers_per_face;
+    if (dens && n_tris) {
+        const int items = (int)n_tris + 1;
+        FLCHK(cnt.ensure(8 * (size_t)items));
+        FLCHK(first.ensure(8 * (size_t)items));
+        FLCHK(err.ensure(8));
+        size_t tbytes = 0;
+        FLCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tbytes, (uint64_t*)nullptr, (uint64_t*)nullptr, items, st));
+        FLCHK(tmp.ensure(tbytes));
+        const uint32_t err0[2] = {0u, 0xFFFFFFFFu};
+        FLCHK(hipMemcpyAsync(err.p, err0, 8, hipMemcpyHostToDevice, st));
+        FLCHK(hipMemsetAsync(cnt.as<uint64_t>() + n_tris, 0, 8, st));
+        hipLaunchKernelGGL(k_fur_count, dim3(blocks(n_tris, 256)), dim3(256), 0, st, d_tri_v, n_tris, p->density, key0,
+                           cnt.as<uint64_t>(), err.as<uint32_t>());
+        FLCHK(hipGetLastError());
+        tbytes = tmp.bytes;
+        FLCHK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tbytes, cnt.as<uint64_t>(), first.as<uint64_t>(), items, st));
+        uint32_t herr[2] = {0, 0};
+        FLCHK(hipMemcpyAsync(&n_fibers, first.as<uint64_t>() + n_tris, 8, hipMemcpyDeviceToHost, st));
+        FLCHK(hipMemcpyAsync(herr, err.p, 8, hipMemcpyDeviceToHost, st));
+        FLCHK(hipStreamSynchronize(st));
+        if (herr[0] & 1u) return "EINVAL:fur: face " + std::to_string(herr[1]) + ": fibre count reaches 65536";
+    } else if (dens) {
+        n_fibers = 0;
+    }
+    perr = fur_total_error(n_fibers, p->verts, n_tris);
+    if (!perr.empty()) return "EINVAL:" + perr;
+    *n_cones = n_fibers * (p->verts - 1);
+    if (!d_base_r0) return std::string();  // the count only
+    if (!d_apex_r1 || (!d_tri_n && p->frame == KHP_FUR_FRAME_NORMAL && n_fibers))
+        return "EINVAL:fur: null array";
+    if (capacity_cones < *n_cones) return "EINVAL:fur: capacity_cones is smaller than the cone count";
+    if (n_fibers) {
+        LnTable t{};
+        const float* ln = fur_ln_table();
+        for (int i = 0; i <= 64; ++i) t.v[i] = ln[i];
+        hipLaunchKernelGGL(k_gen_fur, dim3(blocks(n_fibers, 256)), dim3(256), 0, st, *p, key0, n_tris,
+                           (uint32_t)n_fibers, p->fibers_per_face, dens ? first.as<uint64_t>() : nullptr, d_tri_v,
+                           d_tri_n, t, (float4*)d_base_r0, (float4*)d_apex_r1);
+        FLCHK(hipGetLastError());
+        FLCHK(hipStreamSynchronize(st));
+    }
     return std::string();
 }
 

@@ -9,6 +9,7 @@
 
 #include <cfloat>
 
+#include "../../include/kirk_hip.h"
 #include "kmath.h"
 
 namespace khp {
@@ -231,13 +232,14 @@ KHD float cone_object_xf(v3 base_in, v3 apex_in, float r0, float r1, const float
 
 // One fiber segment c (vertices c, c+1) -> cone: base pulled back by 0.8 % of
 // the segment, base radius shrunk 5 % (c <= 3) or 10 %.
-KHD void fiber_segment(const float* P, const float* R, uint32_t c, float* ob, float* oa) {
-    v3 basepos = ld3(P + 3 * c), apexpos = ld3(P + 3 * (c + 1));
-    float br = R[c];
+KHD void fiber_segment_at(v3 basepos, v3 apexpos, float br, float ar, uint32_t c, float* ob, float* oa) {
     basepos = basepos - (apexpos - basepos) * 0.008f;
     br -= (c > 3) ? 0.1f * br : 0.05f * br;
     ob[0] = basepos.x; ob[1] = basepos.y; ob[2] = basepos.z; ob[3] = br;
-    oa[0] = apexpos.x; oa[1] = apexpos.y; oa[2] = apexpos.z; oa[3] = R[c + 1];
+    oa[0] = apexpos.x; oa[1] = apexpos.y; oa[2] = apexpos.z; oa[3] = ar;
+}
+KHD void fiber_segment(const float* P, const float* R, uint32_t c, float* ob, float* oa) {
+    fiber_segment_at(ld3(P + 3 * c), ld3(P + 3 * (c + 1)), R[c], R[c + 1], c, ob, oa);
 }
 
 // glm::mat4(1) * vec4(p, w), in glm's operation order ((m0 x + m1 y) + (m2 z + m3 w)):
@@ -290,6 +292,59 @@ KHD void fiber_tube_triangle(const float* P, const float* R, uint32_t c, uint32_
     of[6] = w.x; of[7] = w.y; of[8] = w.z;
 }
 
+// ---- the addFurToFaces recurrence (Mesh.cpp:114-142), one vertex at a time ----
+// A strand in flight: the last vertex written (pos, radius) and the frame it
+// grows in.  `up` is the local y the strand lifts along, `tan` the local z it
+// leans along; scale multiplies KIRK's metre constants (x * 1.0f is exact).
+struct Strand {
+    v3 pos, up, tan;
+    float radius, scale;
+    uint32_t verts;
+};
+
+// Vertex 0: the root sunk by 0.003 ("move start position down", Mesh.cpp:114).
+KHD Strand strand_begin(v3 root, v3 up, v3 tan, float root_r, float scale, uint32_t verts) {
+    Strand s;
+    s.pos = root - up * (0.003f * scale);
+    s.up = up;
+    s.tan = tan;
+    s.radius = root_r;
+    s.scale = scale;
+    s.verts = verts;
+    return s;
+}
+
+// Vertex k (1 .. verts-1) from vertex k-1: KIRK's loop variable is i = verts - k + 1
+// (Mesh.cpp:124-139); the last vertex gets the tip radius 0.001 (Mesh.cpp:142).
+// lnt[i] = (float)ln(i).
+KHD void strand_next(Strand& s, uint32_t k, const float* lnt) {
+    const int i = (int)(s.verts - k + 1);
+    const float off_y = (lnt[i] / 90.0f) * s.scale;
+    s.pos = (s.pos + s.up * off_y) + s.tan * (0.06f * s.scale);
+    s.radius -= s.radius / ((float)i + 5.0f);
+    if (k + 1 == s.verts) s.radius = 0.001f * s.scale;
+}
+
+// The whole strand into P [verts][3] / R [verts].
+KHD void strand_fill(Strand s, const float* lnt, float* P, float* R) {
+    P[0] = s.pos.x; P[1] = s.pos.y; P[2] = s.pos.z;
+    R[0] = s.radius;
+    for (uint32_t k = 1; k < s.verts; ++k) {
+        strand_next(s, k, lnt);
+        P[3 * k] = s.pos.x; P[3 * k + 1] = s.pos.y; P[3 * k + 2] = s.pos.z;
+        R[k] = s.radius;
+    }
+}
+
+// A unit tangent of the unit normal n, turned by psi = 2 pi u about it.
+KHD v3 random_tangent(v3 n, float u) {
+    v3 ref = fabsf(n.y) < 0.9f ? mk(0.0f, 1.0f, 0.0f) : mk(1.0f, 0.0f, 0.0f);
+    v3 t0 = normalize(cross(n, ref));
+    v3 b0 = cross(n, t0);
+    float psi = 2.0f * PIF * u;
+    return t0 * k_cosf(psi) + b0 * k_sinf(psi);
+}
+
 // Strand s of the seeded hairball: root uniform on the sphere, the
 // addFurToFaces recurrence in the root's tangent frame.  lnt[i] = (float)ln(i).
 KHD void hairball_strand(uint32_t s, uint32_t verts, v3 C, float ball_r, float root_r, uint32_t key0,
@@ -300,26 +355,60 @@ KHD void hairball_strand(uint32_t s, uint32_t verts, v3 C, float ball_r, float r
     float rxy = sqrtf(gmax(0.0f, 1.0f - z * z));
     float phi = 2.0f * PIF * u1;
     v3 nrm = mk(rxy * k_cosf(phi), z, rxy * k_sinf(phi));
-    v3 ref = fabsf(nrm.y) < 0.9f ? mk(0.0f, 1.0f, 0.0f) : mk(1.0f, 0.0f, 0.0f);
-    v3 t0 = normalize(cross(nrm, ref));
-    v3 b0 = cross(nrm, t0);
-    float psi = 2.0f * PIF * u2;
-    v3 tan = t0 * k_cosf(psi) + b0 * k_sinf(psi);
-    v3 pos = C + nrm * ball_r;
-    pos = pos - nrm * 0.003f;  // "move start position down" (Mesh.cpp:115)
-    float radius = root_r;
-    P[0] = pos.x; P[1] = pos.y; P[2] = pos.z;
-    R[0] = radius;
-    uint32_t k = 1;
-    for (int i = (int)verts; i > 1; --i, ++k) {
-        float off_y = lnt[i] / 90.0f;
-        v3 point = (pos + nrm * off_y) + tan * 0.06f;
-        radius -= radius / ((float)i + 5.0f);
-        P[3 * k] = point.x; P[3 * k + 1] = point.y; P[3 * k + 2] = point.z;
-        R[k] = radius;
-        pos = point;
+    v3 tan = random_tangent(nrm, u2);
+    strand_fill(strand_begin(C + nrm * ball_r, nrm, tan, root_r, 1.0f, verts), lnt, P, R);
+}
+
+// ---- fur on a triangle mesh (Mesh::addFurToFaces, Mesh.cpp:82-148) -------------
+constexpr uint32_t FUR_KEY_SALT = 0x46555221u;   // "FUR!"
+constexpr uint32_t FUR_MAX_PER_FACE = 65535u;
+constexpr uint32_t FUR_COUNT_BAD = 0xFFFFFFFFu;  // fur_face_count: the face's count would reach 65,536
+
+// The keys depend on (seed, face, fibre within the face) only, never on the
+// global fibre number: a face's fur does not change when another face's count does.
+KHD uint32_t fur_key0(uint32_t seed) { return lowbias32(seed ^ FUR_KEY_SALT); }
+KHD uint32_t fur_face_key(uint32_t key0, uint32_t f) { return lowbias32(key0 ^ f); }
+KHD uint32_t fur_fiber_key(uint32_t face_key, uint32_t j) { return lowbias32(face_key + j * 0x9E3779B9u); }
+
+// true when |a| is finite and >= 1e-6; *len = |a|
+KHD bool fur_usable(v3 a, float* len) {
+    *len = length(a);
+    return *len >= 1e-6f && *len <= FLT_MAX;
+}
+
+// Density mode: fibres of face (a, b, c) = floor(area * density + u), u drawn from
+// the face's own key (stochastic rounding: small faces still get their share).
+// A NaN area gives 0; FUR_COUNT_BAD when the count would reach 65,536.
+KHD uint32_t fur_face_count(v3 a, v3 b, v3 c, float density, uint32_t face_key) {
+    const float area = 0.5f * length(cross(b - a, c - a));
+    const float x = area * density + draw_u01(face_key, 0);
+    if (!(x >= 0.0f)) return 0u;
+    if (x >= 65536.0f) return FUR_COUNT_BAD;
+    return (uint32_t)floorf(x);
+}
+
+// Vertex 0 of fibre j of face f (tv / tn: the face's 9 vertex / normal floats).
+KHD Strand fur_strand_begin(const khp_fur_params& p, uint32_t key0, uint32_t f, uint32_t j, const float* tv,
+                            const float* tn) {
+    const uint32_t key = fur_fiber_key(fur_face_key(key0, f), j);
+    const v3 a = ld3(tv), b = ld3(tv + 3), c = ld3(tv + 6);
+    float r1 = draw_u01(key, 0), r2 = draw_u01(key, 1);
+    if (r1 + r2 >= 1.0f) {  // "Otherwise point would be outside the triangle" (Mesh.cpp:110)
+        r1 = 1.0f - r1;
+        r2 = 1.0f - r2;
     }
-    R[verts - 1] = 0.001f;  // Mesh.cpp:142
+    const v3 root = (a + (b - a) * r1) + (c - a) * r2;  // Mesh.cpp:112
+    if (p.frame == KHP_FUR_FRAME_KIRK)  // lift along +y, lean along +z of the mesh's own space
+        return strand_begin(root, mk(0.0f, 1.0f, 0.0f), mk(0.0f, 0.0f, 1.0f), p.root_radius, p.scale, p.verts);
+    float len;
+    v3 n = (ld3(tn) * ((1.0f - r1) - r2) + ld3(tn + 3) * r1) + ld3(tn + 6) * r2;
+    if (!fur_usable(n, &len)) n = cross(b - a, c - a);  // the geometric normal
+    n = fur_usable(n, &len) ? n * (1.0f / len) : mk(0.0f, 1.0f, 0.0f);
+    const v3 comb = mk(p.comb[0], p.comb[1], p.comb[2]);
+    const v3 lean = comb - n * dot(comb, n);  // the comb direction in the tangent plane
+    const v3 tan = (!is_zero(comb) && fur_usable(lean, &len)) ? lean * (1.0f / len)
+                                                              : random_tangent(n, draw_u01(key, 2));
+    return strand_begin(root, n, tan, p.root_radius, p.scale, p.verts);
 }
 
 }  // namespace khp

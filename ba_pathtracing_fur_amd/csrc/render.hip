@@ -3188,6 +3188,24 @@ extern "C" khp_status khp_gen_hairball_tris_device(khp_ctx* c, uint32_t n, uint3
     return KHP_OK;
 }
 
+extern "C" khp_status khp_gen_fur_device(khp_ctx* c, const khp_fur_params* p, uint32_t n_tris, const float* d_tri_v,
+                                         const float* d_tri_n, uint64_t capacity_cones, float* d_base_r0,
+                                         float* d_apex_r1, uint64_t* n_cones) {
+    if (c) {  // complete asynchronous frames first
+        khp_status dr = drain(c);
+        if (dr != KHP_OK) return dr;
+    }
+    if (!c) return fail(KHP_EINVAL, "ctx is null");
+    HIPCHK(hipSetDevice(c->device));
+    std::string err = device_gen_fur(p, n_tris, d_tri_v, d_tri_n, capacity_cones, d_base_r0, d_apex_r1, n_cones,
+                                     c->stream);
+    if (!err.empty()) {
+        if (err.rfind("EINVAL:", 0) == 0) return fail(KHP_EINVAL, err.substr(7));
+        return fail(KHP_EDEVICE, err);
+    }
+    return KHP_OK;
+}
+
 extern "C" khp_status khp_device_alloc(khp_ctx* c, size_t bytes, void** out) {
     if (!c || !out) return fail(KHP_EINVAL, "null argument");
     HIPCHK(hipSetDevice(c->device));

@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
 #include <thread>
 
 namespace khp {
@@ -753,5 +754,97 @@ extern "C" khp_status khp_gen_torus(uint32_t nu, uint32_t nv, const float center
                 tri_n[3 * k] = tn[q].x; tri_n[3 * k + 1] = tn[q].y; tri_n[3 * k + 2] = tn[q].z;
             }
         }
+    return KHP_OK;
+}
+
+// ---- fur on a triangle mesh: Mesh::addFurToFaces (Mesh.cpp:82-148) ---------------
+extern "C" void khp_fur_params_defaults(khp_fur_params* p) {
+    if (!p) return;
+    *p = khp_fur_params{};
+    p->fibers_per_face = 5;   // Demo/main.cpp:235: addFurFibersToAllMeshes(5, 10, 0.004)
+    p->density = 0.0f;
+    p->verts = 10;
+    p->root_radius = 0.004f;
+    p->scale = 1.0f;
+    p->frame = KHP_FUR_FRAME_KIRK;
+    p->seed = 0x4B49524Bu;
+}
+
+namespace khp {
+
+const float* fur_ln_table() {  // glm::log((float)i), as khp_gen_hairball
+    static const struct Table {
+        float v[65];
+        Table() {
+            v[0] = 0.0f;
+            for (int i = 1; i <= 64; ++i) v[i] = (float)log((double)i);
+        }
+    } t;
+    return t.v;
+}
+
+std::string fur_params_error(const khp_fur_params* p) {
+    if (!p) return "fur: params is null";
+    if (!(p->root_radius > 0.0f)) return "fur: root_radius has to be > 0";  // Mesh.cpp:85-89
+    if (!(p->scale > 0.0f)) return "fur: scale has to be > 0";
+    if (p->verts < 2 || p->verts > 64) return "fur: verts outside 2..64";
+    if (p->frame != KHP_FUR_FRAME_KIRK && p->frame != KHP_FUR_FRAME_NORMAL) return "fur: unknown frame";
+    if (!(p->density >= 0.0f) || !std::isfinite(p->density)) return "fur: density negative or not finite";
+    if (p->density == 0.0f && p->fibers_per_face > FUR_MAX_PER_FACE)
+        return "fur: fibers_per_face reaches 65536";
+    return std::string();
+}
+
+std::string fur_total_error(uint64_t n_fibers, uint32_t verts, uint32_t n_tris) {
+    if (n_fibers * (uint64_t)(verts - 1) > (uint64_t)UINT32_MAX - n_tris)
+        return "fur: more than UINT32_MAX - n_tris cones";
+    return std::string();
+}
+
+}  // namespace khp
+
+extern "C" khp_status khp_fur_count(const khp_fur_params* p, uint32_t n_tris, const float* tri_v, uint64_t* n_fibers,
+                                    uint32_t* face_first) {
+    std::string err = fur_params_error(p);
+    if (!err.empty()) return fail(KHP_EINVAL, err);
+    if (!n_fibers) return fail(KHP_EINVAL, "fur: n_fibers is null");
+    const bool dens = p->density > 0.0f;
+    if (dens && n_tris && !tri_v) return fail(KHP_EINVAL, "fur: tri_v is null");
+    const uint32_t key0 = fur_key0(p->seed);
+    uint64_t total = 0;
+    for (uint32_t f = 0; f < n_tris; ++f) {
+        uint32_t cnt = p->fibers_per_face;
+        if (dens) {
+            const float* v = tri_v + 9 * (size_t)f;
+            cnt = fur_face_count(ld3(v), ld3(v + 3), ld3(v + 6), p->density, fur_face_key(key0, f));
+            if (cnt == FUR_COUNT_BAD)
+                return fail(KHP_EINVAL, "fur: face " + std::to_string(f) + ": fibre count reaches 65536");
+        }
+        if (face_first) face_first[f] = (uint32_t)total;
+        total += cnt;
+        err = fur_total_error(total, p->verts, n_tris);
+        if (!err.empty()) return fail(KHP_EINVAL, err);
+    }
+    if (face_first) face_first[n_tris] = (uint32_t)total;
+    *n_fibers = total;
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_gen_fur(const khp_fur_params* p, uint32_t n_tris, const float* tri_v, const float* tri_n,
+                                  float* positions, float* radii) {
+    std::vector<uint32_t> first((size_t)n_tris + 1);
+    uint64_t n = 0;
+    khp_status st = khp_fur_count(p, n_tris, tri_v, &n, first.data());
+    if (st != KHP_OK) return st;
+    if (n == 0) return KHP_OK;
+    if (!tri_v || (!tri_n && p->frame == KHP_FUR_FRAME_NORMAL) || !positions || !radii)
+        return fail(KHP_EINVAL, "fur: null array");
+    const uint32_t key0 = fur_key0(p->seed);
+    const float* lnt = fur_ln_table();
+    for (uint32_t f = 0; f < n_tris; ++f)
+        for (uint32_t k = first[f]; k < first[f + 1]; ++k)
+            strand_fill(fur_strand_begin(*p, key0, f, k - first[f], tri_v + 9 * (size_t)f,
+                                         tri_n ? tri_n + 9 * (size_t)f : nullptr),
+                        lnt, positions + (size_t)k * p->verts * 3, radii + (size_t)k * p->verts);
     return KHP_OK;
 }

@@ -122,6 +122,12 @@ void owned_pixels(uint32_t W, uint32_t H, uint32_t T, uint32_t rank, uint32_t nr
 std::string gather_plan(uint32_t W, uint32_t H, uint32_t T, int nranks, int rank, int root,
                         std::vector<uint64_t>& counts, std::vector<uint32_t>& flat);
 
+// Fur on a mesh (khp_gen_fur / khp_gen_fur_device): the parameter checks both
+// share (empty string: fine), the cone-count limit, and lnt[i] = (float)ln(i), i <= 64.
+std::string fur_params_error(const khp_fur_params* p);
+std::string fur_total_error(uint64_t n_fibers, uint32_t verts, uint32_t n_tris);
+const float* fur_ln_table();
+
 // Per-thread message behind khp_last_error(); every failing entry point sets it.
 khp_status fail(khp_status s, const std::string& msg);
 // tonemap_host.cpp: KIRK's sequential float running sum s <- (float)((double)s + l[k])

@@ -158,6 +158,29 @@ class Tonemap(ctypes.Structure):
         return t
 
 
+FUR_FRAME_KIRK, FUR_FRAME_NORMAL = 0, 1
+
+
+class FurParams(ctypes.Structure):
+    """khp_fur_params (ABI 14, 44 bytes): Mesh::addFurToFaces' arguments and the seeded extensions."""
+    _fields_ = [("fibers_per_face", c_uint32), ("density", c_float), ("verts", c_uint32), ("root_radius", c_float),
+                ("scale", c_float), ("frame", c_uint32), ("comb", F3), ("seed", c_uint32), ("reserved", c_uint32)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "FurParams":
+        """khp_fur_params_defaults (the Demo's addFurFibersToAllMeshes(5, 10, 0.004)) with fields changed."""
+        p = cls()
+        load_library().khp_fur_params_defaults(ctypes.byref(p))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise AttributeError(f"khp_fur_params has no field {k}")
+            if k == "comb":
+                p.comb[:] = [float(x) for x in v]
+            else:
+                setattr(p, k, v)
+        return p
+
+
 # every symbol the header declares (checked by tests/test_abi.py)
 EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "khp_set_scene", "khp_build_accel",
             "khp_render", "khp_read_framebuffer", "khp_trace_closest", "khp_trace_any", "khp_get_stats",
@@ -170,10 +193,11 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_sync", "khp_ctx_params_defaults", "khp_set_params", "khp_get_params", "khp_debug_shadow_queue",
             "khp_bdpt_params_defaults", "khp_set_bdpt", "khp_get_bdpt", "khp_gather_plan",
             "khp_read_rgba8_async", "khp_snapshot_wait", "khp_comm_init_local", "khp_comm_set_timeout",
-            "khp_tonemap_log_sum", "khp_set_camera", "khp_debug_comm_wait"]
+            "khp_tonemap_log_sum", "khp_set_camera", "khp_debug_comm_wait", "khp_fur_params_defaults",
+            "khp_fur_count", "khp_gen_fur", "khp_gen_fur_device"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _lib = None
 
@@ -254,6 +278,11 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_fibers_to_cones": (c_int, [c_uint32, c_uint32, P(c_float), P(c_float), P(c_float), P(c_float)]),
         "khp_gen_hairball": (c_int, [c_uint32, c_uint32, P(c_float), c_float, c_float, c_uint32, P(c_float),
                                      P(c_float)]),
+        "khp_fur_params_defaults": (None, [P(FurParams)]),
+        "khp_fur_count": (c_int, [P(FurParams), c_uint32, P(c_float), P(c_uint64), P(c_uint32)]),
+        "khp_gen_fur": (c_int, [P(FurParams), c_uint32, P(c_float), P(c_float), P(c_float), P(c_float)]),
+        "khp_gen_fur_device": (c_int, [c_void_p, P(FurParams), c_uint32, c_void_p, c_void_p, c_uint64, c_void_p,
+                                       c_void_p, P(c_uint64)]),
         "khp_gen_icosphere": (c_int, [c_uint32, P(c_float), c_float, P(c_float), P(c_float)]),
         "khp_gen_torus": (c_int, [c_uint32, c_uint32, P(c_float), c_float, c_float, P(c_float), P(c_float)]),
         "khp_debug_queue": (c_int, [c_void_p, P(c_uint32), P(c_float), P(c_float)]),

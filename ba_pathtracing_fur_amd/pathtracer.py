@@ -120,9 +120,25 @@ class HipContext:
                 "khp_gen_hairball_device")
         return base, apex, nc
 
+    def fur_device(self, tri_v_buf: DeviceBuffer, tri_n_buf: "DeviceBuffer | None", n_tris: int, **params):
+        """Fur on a mesh that lives in HBM (khp_gen_fur_device; params: khp_fur_params
+        fields): (base_r0, apex_r1, n_cones), the cones of scenes.fur_on_mesh followed
+        by add_fibers, for set_scene_device(..., cones=(base, apex, n, mat))."""
+        p = N.FurParams.defaults(**params)
+        tv = tri_v_buf.ptr if tri_v_buf is not None else None
+        tn = tri_n_buf.ptr if tri_n_buf is not None else None
+        n = ctypes.c_uint64()
+        N.check(self.lib, self.lib.khp_gen_fur_device(self.ptr, ctypes.byref(p), n_tris, tv, tn, 0, None, None,
+                                                      ctypes.byref(n)), "khp_gen_fur_device")
+        nc = n.value
+        base, apex = DeviceBuffer(self, 16 * nc), DeviceBuffer(self, 16 * nc)
+        N.check(self.lib, self.lib.khp_gen_fur_device(self.ptr, ctypes.byref(p), n_tris, tv, tn, nc, base.ptr, apex.ptr,
+                                                      ctypes.byref(n)), "khp_gen_fur_device")
+        return base, apex, nc
+
     def set_scene_device(self, scene: SceneData, cones=None):
         """khp_set_scene_device: the scene's geometry copied to HBM first, or, with
-        cones=(base_r0, apex_r1, n, material) from hairball_device, those cones in
+        cones=(base_r0, apex_r1, n, material) from hairball_device / fur_device, those cones in
         place of the scene's own (which must then be empty)."""
         d = scene.desc()
         keep = []

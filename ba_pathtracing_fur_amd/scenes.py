@@ -223,6 +223,15 @@ class SceneData:
                 "khp_fibers_to_cones")
         self.add_cones(base, apex, mat, model)
 
+    def add_fur(self, tri_v: np.ndarray, tri_n: np.ndarray, mat: int, as_triangles: bool = False,
+                model: int | None = None, **params):
+        """Mesh::addFurToFaces on the triangles (tri_v, tri_n) (fur_on_mesh; params:
+        khp_fur_params fields), then add_fibers.  The fur is in the mesh's own space:
+        pass the node transform of a transformed mesh as `model`."""
+        pos, rad = fur_on_mesh(tri_v, tri_n, **params)
+        if len(rad):
+            self.add_fibers(pos, rad, mat, as_triangles=as_triangles, model=model)
+
     def add_cones(self, base_r0: np.ndarray, apex_r1: np.ndarray, mat: int, model: int | None = None):
         """Cones (Cylinder ctor args); model: index of a node transform (add_cone_model),
         None = world space (an identity model once any cone of the scene has one)."""
@@ -365,6 +374,36 @@ def hairball(n_strands: int, center, ball_radius: float, root_radius: float = 0.
     return pos, rad
 
 
+def fur_count(tri_v: np.ndarray, **params):
+    """khp_fur_count: (n_fibers, face_first [n_tris + 1]) of fur_on_mesh with the same params."""
+    lib = N.load_library()
+    p = N.FurParams.defaults(**params)
+    v = np.ascontiguousarray(tri_v, np.float32).reshape(-1, 3, 3)
+    n = ctypes.c_uint64()
+    first = np.zeros(len(v) + 1, np.uint32)
+    N.check(lib, lib.khp_fur_count(ctypes.byref(p), len(v), N.fptr(v), ctypes.byref(n), N.uptr(first)), "khp_fur_count")
+    return n.value, first
+
+
+def fur_on_mesh(tri_v: np.ndarray, tri_n: np.ndarray, **params):
+    """Fur fibres on a triangle mesh (khp_gen_fur, Mesh::addFurToFaces, Mesh.cpp:82-148):
+    (positions [n][verts][3], radii [n][verts]), face-major.  params: khp_fur_params
+    fields (fibers_per_face, density, verts, root_radius, scale, frame, comb, seed);
+    the defaults are the Demo's addFurFibersToAllMeshes(5, 10, 0.004)."""
+    lib = N.load_library()
+    p = N.FurParams.defaults(**params)
+    v = np.ascontiguousarray(tri_v, np.float32).reshape(-1, 3, 3)
+    nn = np.ascontiguousarray(tri_n, np.float32).reshape(-1, 3, 3)
+    if len(nn) != len(v):
+        raise ValueError("tri_n must hold three normals per triangle of tri_v")
+    n, _ = fur_count(v, **params)
+    pos = np.empty((n, p.verts, 3), np.float32)
+    rad = np.empty((n, p.verts), np.float32)
+    N.check(lib, lib.khp_gen_fur(ctypes.byref(p), len(v), N.fptr(v), N.fptr(nn), N.fptr(pos), N.fptr(rad)),
+            "khp_gen_fur")
+    return pos, rad
+
+
 def icosphere(subdiv: int, center, radius: float):
     lib = N.load_library()
     n = 20 * 4 ** subdiv
@@ -459,6 +498,37 @@ def config3_device(ctx, width=1920, height=1080, n_strands=1_000_000, bsdf="Mars
     ctx.set_scene_device(sd, cones=(base, apex, nc, 1))
     base.free()
     apex.free()
+    return sd
+
+
+def furry(width=1920, height=1080, subdiv=3, fibers_per_face=5, bsdf="MarschnerHairBSDF",
+          frame=N.FUR_FRAME_NORMAL, **params) -> SceneData:
+    """A Lambert icosphere (r=1.0, 20 * 4^subdiv faces) on config 3's plane, light and
+    camera, with fur on its faces at the Demo's parameters (10 vertices, root radius
+    0.004; Demo/main.cpp:235)."""
+    sd = config3(width, height, 0, bsdf)
+    sd.name = f"furry_{subdiv}_{fibers_per_face}"
+    v, n = icosphere(subdiv, (0.0, 1.0, 0.0), 1.0)
+    sd.add_triangles(v, n, sd.add_material(material(diffuse=(0.725, 0.725, 0.725))))
+    sd.add_fur(v, n, 1, fibers_per_face=fibers_per_face, frame=frame, **params)
+    return sd
+
+
+def furry_device(ctx, width=1920, height=1080, subdiv=3, fibers_per_face=5, bsdf="MarschnerHairBSDF",
+                 frame=N.FUR_FRAME_NORMAL, **params) -> SceneData:
+    """furry with the fur generated and flattened on the GPU of `ctx` from the mesh in
+    HBM (khp_gen_fur_device + khp_set_scene_device).  The same objects in the same
+    order as furry, so the same tree and frames.  Returns the host part (plane,
+    sphere, materials, lights, camera); the cones live in HBM."""
+    from .pathtracer import DeviceBuffer
+    sd = furry(width, height, subdiv, 0, bsdf, frame, **params)
+    sd.name = f"furry_{subdiv}_{fibers_per_face}_device"
+    v, n = sd.tri_v[2:], sd.tri_n[2:]   # the sphere, after the plane's two triangles
+    dv, dn = DeviceBuffer.from_array(ctx, v), DeviceBuffer.from_array(ctx, n)
+    base, apex, nc = ctx.fur_device(dv, dn, len(v), fibers_per_face=fibers_per_face, frame=frame, **params)
+    ctx.set_scene_device(sd, cones=(base, apex, nc, 1))
+    for b in (dv, dn, base, apex):
+        b.free()
     return sd
 
 
@@ -624,4 +694,5 @@ def textured(width=64, height=48, n_strands=600, env: str = "cube") -> SceneData
 
 def build_config(name: str, **kw) -> SceneData:
     return {"config1": config1, "config2": config2, "config3": config3, "config5": config5, "zoo": zoo,
-            "transformed": transformed_hairball, "textured": textured}[name](**kw)
+            "transformed": transformed_hairball, "textured": textured, "furry": furry,
+            "furry_device": furry_device}[name](**kw)

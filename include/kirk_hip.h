@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define KHP_ABI_VERSION 13
+#define KHP_ABI_VERSION 14
 
 typedef struct khp_ctx khp_ctx;
 
@@ -655,6 +655,75 @@ khp_status khp_fibers_to_triangles(uint32_t n_fibers, uint32_t verts_per_fiber, 
 khp_status khp_gen_hairball(uint32_t n_strands, uint32_t verts, const float center[3],
                             float ball_radius, float root_radius, uint32_t seed,
                             float* positions, float* radii);
+/* ---- ABI 14: fur on an arbitrary triangle mesh ------------------------------
+ * Replaces Mesh::addFurToFaces (Common/Mesh.cpp:82-148), which
+ * SceneGraph::addFurFibersToAllMeshes(5, 10, 0.004) runs on every mesh
+ * (Demo/main.cpp:235): per face, fibres rooted at uniform points of the
+ * triangle, each following the recurrence of Mesh.cpp:114-142.
+ *
+ * Every fibre draws from its own key, a function of (seed, face index, fibre
+ * index within the face) only: a face's fur does not change when another
+ * face's count or shape does.  Root (Mesh.cpp:104-112): two draws r1, r2,
+ * mirrored (1 - r1, 1 - r2) when r1 + r2 >= 1, root = (a + r1 (b - a)) +
+ * r2 (c - a).  KIRK draws from [0, 1], the key's draws lie in [0, 1): a
+ * difference of measure zero.  KIRK seeds from std::random_device; here the
+ * result is a function of `seed`, bit for bit on host and device. */
+#define KHP_FUR_FRAME_KIRK   0  /* Mesh.cpp as written: lift along +y, lean along +z of the mesh's own space */
+#define KHP_FUR_FRAME_NORMAL 1  /* the same recurrence in the root's tangent frame (as the seeded hairball):
+                                   local y = shading normal at the root, local z = lean direction */
+typedef struct {
+    uint32_t fibers_per_face;  /* KIRK's count (Demo: 5); used when density == 0, at most 65,535 */
+    float    density;          /* > 0: fibres per unit area instead.  A face of area A = 0.5 |(b-a) x (c-a)|
+                                  gets floor(A * density + u) fibres, u a draw of the face's own key
+                                  (stochastic rounding: small faces keep their share); a NaN area gives 0 */
+    uint32_t verts;            /* vertices per fibre, 2..64 (Demo: 10) */
+    float    root_radius;      /* > 0 (Demo: 0.004); KIRK refuses <= 0, Mesh.cpp:85-89 */
+    float    scale;            /* > 0; multiplies KIRK's metre constants (0.003 sink, ln(i)/90 lift, 0.06 lean,
+                                  0.001 tip radius); 1 = KIRK's.  x * 1.0f is exact, so 1 changes no bit */
+    uint32_t frame;            /* KHP_FUR_FRAME_* */
+    float    comb[3];          /* FRAME_NORMAL only: lean direction before projection into the tangent plane
+                                  (used when the projection is at least 1e-6 long); (0,0,0) = a seeded random
+                                  tangent per fibre, as the hairball does */
+    uint32_t seed;
+    uint32_t reserved;         /* 0 */
+} khp_fur_params;              /* 44 bytes */
+/* Fills the Demo's call: 5, 0, 10, 0.004, 1, KIRK, 0 0 0, 0x4B49524B. */
+void khp_fur_params_defaults(khp_fur_params* out);
+
+/* FRAME_NORMAL: the normal at the root is normalize((1-r1-r2) na + r1 nb + r2 nc); when
+ * that sum is shorter than 1e-6 or not finite, the geometric normal
+ * normalize((b-a) x (c-a)), and (0,1,0) when that fails too.
+ *
+ * All three calls return KHP_EINVAL when root_radius <= 0, scale <= 0, verts is
+ * outside 2..64, frame is unknown, density is negative or not finite, a face's
+ * count would reach 65,536 (the message names the face), or the cones
+ * n_fibers * (verts - 1) exceed UINT32_MAX - n_tris (a scene's object ids are
+ * 32 bits).  fibers_per_face == 0 with density == 0 is a valid empty result.
+ *
+ * Host only: the number of fibres, and (face_first nullable, [n_tris + 1]) the
+ * exclusive prefix of the per-face counts; face f owns fibres
+ * [face_first[f], face_first[f+1]).  tri_v as khp_scene.tri_v (read in density
+ * mode only). */
+khp_status khp_fur_count(const khp_fur_params* p, uint32_t n_tris, const float* tri_v, uint64_t* n_fibers,
+                         uint32_t* face_first);
+/* The fibres: positions [n_fibers][verts][3], radii [n_fibers][verts], face-major,
+ * the fibre index within the face minor.  They feed khp_fibers_to_cones /
+ * khp_fibers_to_triangles unchanged.  tri_n (as khp_scene.tri_n) is read with
+ * FRAME_NORMAL only.  The fur is in the mesh's own space: a node transform goes
+ * through khp_scene.cone_models. */
+khp_status khp_gen_fur(const khp_fur_params* p, uint32_t n_tris, const float* tri_v, const float* tri_n,
+                       float* positions, float* radii);
+/* khp_gen_fur followed by khp_fibers_to_cones, on the device: d_tri_v / d_tri_n
+ * and the outputs are device arrays of ctx's GPU; writes *n_cones = n_fibers *
+ * (verts - 1) cones (float4 base.xyz r0 / apex.xyz r1), bit-identical to the
+ * host pair and usable as khp_scene.cone_base_r0 / cone_apex_r1 of
+ * khp_set_scene_device.  d_base_r0 == NULL: *n_cones only.  capacity_cones
+ * (the cones the arrays hold) smaller than the count: KHP_EINVAL, nothing
+ * written. */
+khp_status khp_gen_fur_device(khp_ctx* ctx, const khp_fur_params* p, uint32_t n_tris, const float* d_tri_v,
+                              const float* d_tri_n, uint64_t capacity_cones, float* d_base_r0, float* d_apex_r1,
+                              uint64_t* n_cones);
+
 /* icosphere with `subdiv` subdivisions: 20*4^subdiv triangles (tri_v/tri_n as khp_scene). */
 khp_status khp_gen_icosphere(uint32_t subdiv, const float center[3], float radius,
                              float* tri_v, float* tri_n);

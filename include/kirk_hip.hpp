@@ -87,6 +87,16 @@ class SceneBuilder {
         check(khp_fibers_to_cones(n_fibers, verts, positions, radii, b.data(), a.data()), "khp_fibers_to_cones");
         add_cones(b.data(), a.data(), nc, mat);
     }
+    // Mesh::addFurToFaces on n_tris triangles (khp_gen_fur, ABI 14), then add_fibers; returns the fibre count
+    uint64_t add_fur(const khp_fur_params& p, const float* tri_v, const float* tri_n, uint32_t n_tris, uint32_t mat) {
+        uint64_t n = 0;
+        check(khp_fur_count(&p, n_tris, tri_v, &n, nullptr), "khp_fur_count");
+        if (n == 0) return 0;
+        std::vector<float> pos(n * p.verts * 3), rad(n * p.verts);
+        check(khp_gen_fur(&p, n_tris, tri_v, tri_n, pos.data(), rad.data()), "khp_gen_fur");
+        add_fibers(pos.data(), rad.data(), (uint32_t)n, p.verts, mat);
+        return n;
+    }
     void add_light(const khp_light& l) { lights_.push_back(l); }
     void set_environment(const khp_environment& e) { env_ = e; }
     void set_camera(const khp_camera& c) { cam_ = c; }
