@@ -1,0 +1,329 @@
+// debug_query.h -- ABI 15 batch queries of the shading functions (test hooks,
+// included by render.hip next to khp_debug_queue).  Each kernel runs one item
+// per thread in a grid-stride loop and calls the __device__ functions the
+// renderer calls -- trace_closest, surface_at, bsdf_sample<KINDS>, bsdf_eval,
+// light_dir, light_isect, light_emit -- so a test can compare them item by item
+// with the oracle and with a float64 reference.  Every index is checked on the
+// host before a launch; the kernels read nothing the host has not validated.
+#pragma once
+
+constexpr uint32_t DBG_MAX_ITEMS = 1u << 20;
+constexpr uint32_t DBG_BLOCK = 256;
+static uint32_t dbg_grid(uint32_t n) { return std::min((n + DBG_BLOCK - 1) / DBG_BLOCK, 1024u); }
+
+__device__ __forceinline__ void st3(float* d, v3 a) {
+    d[0] = a.x;
+    d[1] = a.y;
+    d[2] = a.z;
+}
+
+template <bool TEX>
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_surface(DevScene S, uint32_t n, const float* orig, const float* dir,
+                                                           float* t_out, int32_t* obj_out, float* nrm, float* uvw,
+                                                           int32_t* mat) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const Ray r = make_ray(ld3(orig + 3 * (size_t)i), ld3(dir + 3 * (size_t)i));
+        Hit h;
+        PrivStack stk;
+        TravStats st{0, 0};
+        trace_closest<false>(S, r, h, stk, st);
+        const v3 zero = mk(0.0f, 0.0f, 0.0f);
+        ShadeCtx s;
+        s.U = s.V = s.W = zero;
+        v3 nn = zero;
+        int32_t m = -1, ob = -1;
+        if (h.slot >= 0) {
+            khp_material mres;
+            nn = surface_at<TEX>(S, r, h, s, mres);
+            const Aux ax = S.aux[h.slot];
+            m = (int32_t)ax.mat;
+            ob = (int32_t)ax.obj;
+        }
+        t_out[i] = h.t;
+        obj_out[i] = ob;
+        st3(nrm + 3 * (size_t)i, nn);
+        st3(uvw + 9 * (size_t)i, s.U);
+        st3(uvw + 9 * (size_t)i + 3, s.V);
+        st3(uvw + 9 * (size_t)i + 6, s.W);
+        mat[i] = m;
+    }
+}
+
+// The hair frame of the object in `slot`, as surface_at loads it: the cone
+// record's rows, or the triangle's tri_frame entry.
+__device__ __forceinline__ void dbg_frame(const DevScene& S, uint32_t slot, ShadeCtx& s) {
+    const Aux ax = S.aux[slot];
+    if (ax.flags & 1u) {
+        const float4* pr = S.prims + 4 * (size_t)slot;
+        const float4 c1 = pr[1], c2 = pr[2], c3 = pr[3];
+        s.U = mk(c1.x, c1.y, c1.z);
+        s.V = mk(c2.x, c2.y, c2.z);
+        s.W = mk(c3.x, c3.y, c3.z);
+    } else {
+        const float* tf = S.tri_frame + 9 * (size_t)ax.obj;
+        s.U = ld3(tf);
+        s.V = ld3(tf + 3);
+        s.W = ld3(tf + 6);
+    }
+}
+
+template <uint32_t KINDS>
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_bsdf_sample(DevScene S, uint32_t n, const uint32_t* slot,
+                                                               const int32_t* mat, const float* in, const float* nrm,
+                                                               const float* sample, const float* hair,
+                                                               const int32_t* flags_in, float* out_dir, float* pdf,
+                                                               float* f, float* sample_out, int32_t* flags_out,
+                                                               int32_t* valid) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        ShadeCtx s;
+        dbg_frame(S, slot[i], s);
+        s.m = &S.mats[mat[i]];
+        s.n = ld3(nrm + 3 * (size_t)i);
+        float sm[2] = {sample[2 * (size_t)i], sample[2 * (size_t)i + 1]};
+        v3 out = mk(0.0f, 0.0f, 0.0f);
+        float pd = 0.0f;
+        int flags = flags_in[i];
+        bool ok = false;
+        const v3 r = bsdf_sample<KINDS>(s, ld3(in + 3 * (size_t)i), s.n, sm, hair[2 * (size_t)i],
+                                        hair[2 * (size_t)i + 1], out, pd, flags, ok);
+        st3(out_dir + 3 * (size_t)i, out);
+        st3(f + 3 * (size_t)i, r);
+        pdf[i] = pd;
+        sample_out[2 * (size_t)i] = sm[0];
+        sample_out[2 * (size_t)i + 1] = sm[1];
+        flags_out[i] = flags;
+        valid[i] = ok ? 1 : 0;
+    }
+}
+
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_bsdf_eval(DevScene S, uint32_t n, const uint32_t* slot,
+                                                             const int32_t* mat, const float* in, const float* nrm,
+                                                             const float* out, float* f) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        ShadeCtx s;
+        dbg_frame(S, slot[i], s);
+        s.m = &S.mats[mat[i]];
+        s.n = ld3(nrm + 3 * (size_t)i);
+        st3(f + 3 * (size_t)i, bsdf_eval(s, ld3(in + 3 * (size_t)i), ld3(out + 3 * (size_t)i)));
+    }
+}
+
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_light_dir(DevScene S, uint32_t n, const int32_t* li, const float* p,
+                                                             const float* u, float* ro, float* rd, float* att) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const DevLight L = S.lights[li[i]];
+        float a = 0.0f;
+        const Ray r = light_dir(L, ld3(p + 3 * (size_t)i), u[2 * (size_t)i], u[2 * (size_t)i + 1], a);
+        st3(ro + 3 * (size_t)i, r.o);
+        st3(rd + 3 * (size_t)i, r.d);
+        att[i] = a;
+    }
+}
+
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_light_isect(DevScene S, uint32_t n, const int32_t* li,
+                                                               const float* orig, const float* dir, uint8_t* hit,
+                                                               float* t_out, float* emit) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const DevLight L = S.lights[li[i]];
+        const Ray r = make_ray(ld3(orig + 3 * (size_t)i), ld3(dir + 3 * (size_t)i));
+        float t = 0.0f;
+        const bool h = light_isect(L, r, t);
+        hit[i] = h ? 1 : 0;
+        t_out[i] = h ? t : 0.0f;
+        st3(emit + 3 * (size_t)i, light_emit(L, r.d));
+    }
+}
+
+// ---- host side ---------------------------------------------------------------------------
+static khp_status dbg_enter(khp_ctx* c, uint32_t n, bool ptrs_ok) {
+    if (!c) return fail(KHP_EINVAL, "ctx is null");
+    KHPCHK(drain(c));  // complete asynchronous frames first
+    if (!ptrs_ok) return fail(KHP_EINVAL, "null argument");
+    if (n == 0 || n > DBG_MAX_ITEMS) return fail(KHP_EINVAL, "n must be in [1, 2^20]");
+    if (!c->scene_set) return fail(KHP_ENOTREADY, "khp_set_scene first");
+    if (!c->built) return fail(KHP_ENOTREADY, "khp_build_accel first");
+    HIPCHK(hipSetDevice(c->device));
+    return KHP_OK;
+}
+
+// The slot of every object (object-id order), from the layout in HBM.
+static khp_status dbg_object_slots(khp_ctx* c, std::vector<uint32_t>& slot_of) {
+    std::vector<Aux> aux(c->n_slots);
+    std::vector<float4> prims(4 * (size_t)c->n_slots);
+    if (c->n_slots) {
+        HIPCHK(hipMemcpyAsync(aux.data(), c->aux.p, sizeof(Aux) * aux.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(prims.data(), c->prims.p, sizeof(float4) * prims.size(), hipMemcpyDeviceToHost, c->stream));
+        KHPCHK(wait_stream(c, c->stream, "the layout read"));
+    }
+    slot_of.assign(c->hs.n_obj, UINT32_MAX);
+    for (uint32_t s = 0; s < c->n_slots; ++s) {
+        uint32_t tag;
+        memcpy(&tag, &prims[4 * (size_t)s].w, sizeof(tag));
+        const bool real = (aux[s].flags & 1u) || tag == TRI_TAG;   // pad slots are zero records
+        if (real && aux[s].obj < slot_of.size()) slot_of[aux[s].obj] = s;
+    }
+    return KHP_OK;
+}
+
+// Validates the (object, material) items of a BSDF query and resolves the objects' slots.
+static khp_status dbg_bsdf_items(khp_ctx* c, uint32_t n, const int32_t* obj, const int32_t* mat, uint32_t kinds_mask,
+                                 std::vector<uint32_t>& slots) {
+    if (kinds_mask != KINDS_ALL && kinds_mask != KINDS_FUR)
+        return fail(KHP_EINVAL, "kinds_mask must be the full set or the fur set (Lambert + Marschner)");
+    std::vector<uint32_t> slot_of;
+    KHPCHK(dbg_object_slots(c, slot_of));
+    slots.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (obj[i] < 0 || (uint32_t)obj[i] >= slot_of.size() || slot_of[obj[i]] == UINT32_MAX)
+            return fail(KHP_EINVAL, "item " + std::to_string(i) + ": object id out of range");
+        if (mat[i] < 0 || (size_t)mat[i] >= c->hs.mats.size())
+            return fail(KHP_EINVAL, "item " + std::to_string(i) + ": material index out of range");
+        const int32_t k = c->hs.mats[mat[i]].bsdf;
+        const uint32_t bit = (k >= 0 && k < KHP_BSDF_COUNT) ? (1u << k) : KINDS_ALL;
+        if (bit & ~kinds_mask)   // the instance has this case compiled out: never launch
+            return fail(KHP_EINVAL, "item " + std::to_string(i) + ": BSDF kind " + std::to_string(k) +
+                                        " is outside kinds_mask");
+        slots[i] = slot_of[obj[i]];
+    }
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_debug_surface(khp_ctx* c, uint32_t n, const float* orig, const float* dir, float* t_out,
+                                        int32_t* obj_out, float* normal, float* uvw, int32_t* mat_out) {
+    KHPCHK(dbg_enter(c, n, orig && dir && t_out && obj_out && normal && uvw && mat_out));
+    DevMem o, d, t, ob, nr, fr, mt;
+    HIPCHK(upload(o, orig, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(d, dir, 3 * (size_t)n, c->stream));
+    HIPCHK(t.ensure(4 * (size_t)n));
+    HIPCHK(ob.ensure(4 * (size_t)n));
+    HIPCHK(nr.ensure(12 * (size_t)n));
+    HIPCHK(fr.ensure(36 * (size_t)n));
+    HIPCHK(mt.ensure(4 * (size_t)n));
+    if (c->S.textured)
+        hipLaunchKernelGGL(k_dbg_surface<true>, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n, o.as<float>(),
+                           d.as<float>(), t.as<float>(), ob.as<int32_t>(), nr.as<float>(), fr.as<float>(), mt.as<int32_t>());
+    else
+        hipLaunchKernelGGL(k_dbg_surface<false>, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n, o.as<float>(),
+                           d.as<float>(), t.as<float>(), ob.as<int32_t>(), nr.as<float>(), fr.as<float>(), mt.as<int32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(t_out, t.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(obj_out, ob.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(normal, nr.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(uvw, fr.p, 36 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(mat_out, mt.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the surface queries"));
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_debug_bsdf_sample(khp_ctx* c, uint32_t n, uint32_t kinds_mask, const int32_t* obj,
+                                            const int32_t* mat, const float* in, const float* normal,
+                                            const float* sample, const float* hair, const int32_t* flags_in,
+                                            float* out_dir, float* pdf, float* f, float* sample_out,
+                                            int32_t* flags_out, int32_t* valid) {
+    KHPCHK(dbg_enter(c, n, obj && mat && in && normal && sample && hair && flags_in && out_dir && pdf && f &&
+                               sample_out && flags_out && valid));
+    std::vector<uint32_t> slots;
+    KHPCHK(dbg_bsdf_items(c, n, obj, mat, kinds_mask, slots));
+    DevMem sl, mt, di, dn, ds, dh, dfl, od, op, of, os, ofl, ov;
+    HIPCHK(upload(sl, slots.data(), (size_t)n, c->stream));
+    HIPCHK(upload(mt, mat, (size_t)n, c->stream));
+    HIPCHK(upload(di, in, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(dn, normal, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(ds, sample, 2 * (size_t)n, c->stream));
+    HIPCHK(upload(dh, hair, 2 * (size_t)n, c->stream));
+    HIPCHK(upload(dfl, flags_in, (size_t)n, c->stream));
+    HIPCHK(od.ensure(12 * (size_t)n));
+    HIPCHK(op.ensure(4 * (size_t)n));
+    HIPCHK(of.ensure(12 * (size_t)n));
+    HIPCHK(os.ensure(8 * (size_t)n));
+    HIPCHK(ofl.ensure(4 * (size_t)n));
+    HIPCHK(ov.ensure(4 * (size_t)n));
+    if (kinds_mask == KINDS_FUR)
+        hipLaunchKernelGGL(k_dbg_bsdf_sample<KINDS_FUR>, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n,
+                           sl.as<uint32_t>(), mt.as<int32_t>(), di.as<float>(), dn.as<float>(), ds.as<float>(),
+                           dh.as<float>(), dfl.as<int32_t>(), od.as<float>(), op.as<float>(), of.as<float>(),
+                           os.as<float>(), ofl.as<int32_t>(), ov.as<int32_t>());
+    else
+        hipLaunchKernelGGL(k_dbg_bsdf_sample<KINDS_ALL>, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n,
+                           sl.as<uint32_t>(), mt.as<int32_t>(), di.as<float>(), dn.as<float>(), ds.as<float>(),
+                           dh.as<float>(), dfl.as<int32_t>(), od.as<float>(), op.as<float>(), of.as<float>(),
+                           os.as<float>(), ofl.as<int32_t>(), ov.as<int32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_dir, od.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(pdf, op.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(f, of.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(sample_out, os.p, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(flags_out, ofl.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(valid, ov.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the BSDF queries"));
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_debug_bsdf_eval(khp_ctx* c, uint32_t n, const int32_t* obj, const int32_t* mat,
+                                          const float* in, const float* normal, const float* out, float* f) {
+    KHPCHK(dbg_enter(c, n, obj && mat && in && normal && out && f));
+    std::vector<uint32_t> slots;
+    KHPCHK(dbg_bsdf_items(c, n, obj, mat, KINDS_ALL, slots));
+    DevMem sl, mt, di, dn, dout, of;
+    HIPCHK(upload(sl, slots.data(), (size_t)n, c->stream));
+    HIPCHK(upload(mt, mat, (size_t)n, c->stream));
+    HIPCHK(upload(di, in, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(dn, normal, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(dout, out, 3 * (size_t)n, c->stream));
+    HIPCHK(of.ensure(12 * (size_t)n));
+    hipLaunchKernelGGL(k_dbg_bsdf_eval, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n, sl.as<uint32_t>(),
+                       mt.as<int32_t>(), di.as<float>(), dn.as<float>(), dout.as<float>(), of.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(f, of.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the BSDF queries"));
+    return KHP_OK;
+}
+
+static khp_status dbg_light_items(khp_ctx* c, uint32_t n, const int32_t* light) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (light[i] < 0 || (size_t)light[i] >= c->hs.lights.size())
+            return fail(KHP_EINVAL, "item " + std::to_string(i) + ": light index out of range");
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_debug_light_dir(khp_ctx* c, uint32_t n, const int32_t* light, const float* point,
+                                          const float* draws, float* ray_orig, float* ray_dir, float* att) {
+    KHPCHK(dbg_enter(c, n, light && point && draws && ray_orig && ray_dir && att));
+    KHPCHK(dbg_light_items(c, n, light));
+    DevMem dl, dp, du, ro, rd, at;
+    HIPCHK(upload(dl, light, (size_t)n, c->stream));
+    HIPCHK(upload(dp, point, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(du, draws, 2 * (size_t)n, c->stream));
+    HIPCHK(ro.ensure(12 * (size_t)n));
+    HIPCHK(rd.ensure(12 * (size_t)n));
+    HIPCHK(at.ensure(4 * (size_t)n));
+    hipLaunchKernelGGL(k_dbg_light_dir, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n, dl.as<int32_t>(),
+                       dp.as<float>(), du.as<float>(), ro.as<float>(), rd.as<float>(), at.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ray_orig, ro.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ray_dir, rd.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(att, at.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the light queries"));
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_debug_light_isect(khp_ctx* c, uint32_t n, const int32_t* light, const float* orig,
+                                            const float* dir, uint8_t* hit, float* t_out, float* emit) {
+    KHPCHK(dbg_enter(c, n, light && orig && dir && hit && t_out && emit));
+    KHPCHK(dbg_light_items(c, n, light));
+    DevMem dl, o, d, dh, dt, de;
+    HIPCHK(upload(dl, light, (size_t)n, c->stream));
+    HIPCHK(upload(o, orig, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(d, dir, 3 * (size_t)n, c->stream));
+    HIPCHK(dh.ensure((size_t)n));
+    HIPCHK(dt.ensure(4 * (size_t)n));
+    HIPCHK(de.ensure(12 * (size_t)n));
+    hipLaunchKernelGGL(k_dbg_light_isect, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n, dl.as<int32_t>(),
+                       o.as<float>(), d.as<float>(), dh.as<uint8_t>(), dt.as<float>(), de.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hit, dh.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(t_out, dt.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(emit, de.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the light queries"));
+    return KHP_OK;
+}

@@ -4964,6 +4964,8 @@ extern "C" khp_status khp_debug_queue(khp_ctx* c, uint32_t* n, float* orig, floa
     return KHP_OK;
 }
 
+#include "debug_query.h"   // ABI 15: khp_debug_surface / _bsdf_sample / _bsdf_eval / _light_dir / _light_isect
+
 extern "C" khp_status khp_read_framebuffer(khp_ctx* c, float* out_rgb) {
     if (c) {  // complete asynchronous frames first
         khp_status dr = drain(c);

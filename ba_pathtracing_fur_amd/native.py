@@ -194,10 +194,11 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_bdpt_params_defaults", "khp_set_bdpt", "khp_get_bdpt", "khp_gather_plan",
             "khp_read_rgba8_async", "khp_snapshot_wait", "khp_comm_init_local", "khp_comm_set_timeout",
             "khp_tonemap_log_sum", "khp_set_camera", "khp_debug_comm_wait", "khp_fur_params_defaults",
-            "khp_fur_count", "khp_gen_fur", "khp_gen_fur_device"]
+            "khp_fur_count", "khp_gen_fur", "khp_gen_fur_device", "khp_debug_surface", "khp_debug_bsdf_sample",
+            "khp_debug_bsdf_eval", "khp_debug_light_dir", "khp_debug_light_isect"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _lib = None
 
@@ -287,6 +288,17 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_gen_torus": (c_int, [c_uint32, c_uint32, P(c_float), c_float, c_float, P(c_float), P(c_float)]),
         "khp_debug_queue": (c_int, [c_void_p, P(c_uint32), P(c_float), P(c_float)]),
         "khp_debug_shadow_queue": (c_int, [c_void_p, P(c_uint32), P(c_float), P(c_float), P(c_float)]),
+        "khp_debug_surface": (c_int, [c_void_p, c_uint32, P(c_float), P(c_float), P(c_float), P(c_int32), P(c_float),
+                                      P(c_float), P(c_int32)]),
+        "khp_debug_bsdf_sample": (c_int, [c_void_p, c_uint32, c_uint32, P(c_int32), P(c_int32), P(c_float), P(c_float),
+                                          P(c_float), P(c_float), P(c_int32), P(c_float), P(c_float), P(c_float),
+                                          P(c_float), P(c_int32), P(c_int32)]),
+        "khp_debug_bsdf_eval": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_int32), P(c_float), P(c_float),
+                                        P(c_float), P(c_float)]),
+        "khp_debug_light_dir": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_float), P(c_float), P(c_float),
+                                        P(c_float), P(c_float)]),
+        "khp_debug_light_isect": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_float), P(c_float), P(c_uint8),
+                                          P(c_float), P(c_float)]),
         "khp_host_build": (c_int, [P(SceneDesc), P(c_uint32), P(c_uint32), P(c_float), P(c_int32), P(c_int32),
                                    P(c_int32), P(c_float), P(c_float)]),
     }

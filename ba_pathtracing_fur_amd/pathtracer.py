@@ -320,6 +320,81 @@ class HipContext:
                 "khp_trace_any")
         return hit.astype(bool)
 
+    # ---- ABI 15 batch queries of the shading functions (test hooks) ----
+    KINDS_ALL = (1 << 11) - 1          # every khp_bsdf_kind
+    KINDS_FUR = (1 << 0) | (1 << 9)    # Lambert + Marschner: the set compiled for fur-only scenes
+
+    def debug_surface(self, orig, direction):
+        """khp_debug_surface: closest hit and the surface there, per ray."""
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+        n = len(o)
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        r = {"t": np.empty(n, np.float32), "obj": np.empty(n, np.int32), "n": np.empty((n, 3), np.float32),
+             "uvw": np.empty((n, 3, 3), np.float32), "mat": np.empty(n, np.int32)}
+        N.check(self.lib, self.lib.khp_debug_surface(self.ptr, n, N.fptr(o), N.fptr(d), N.fptr(r["t"]), ip(r["obj"]),
+                                                     N.fptr(r["n"]), N.fptr(r["uvw"]), ip(r["mat"])),
+                "khp_debug_surface")
+        return r
+
+    def debug_bsdf_sample(self, obj, mat, ray_in, normal, sample, hair, flags_in, kinds_mask=None):
+        """khp_debug_bsdf_sample on n items; kinds_mask: KINDS_ALL (default) or KINDS_FUR."""
+        ob = np.ascontiguousarray(obj, np.int32).reshape(-1)
+        n = len(ob)
+        mt = np.ascontiguousarray(mat, np.int32).reshape(-1)
+        ri = np.ascontiguousarray(ray_in, np.float32).reshape(-1, 3)
+        nn = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        sm = np.ascontiguousarray(sample, np.float32).reshape(-1, 2)
+        hu = np.ascontiguousarray(hair, np.float32).reshape(-1, 2)
+        fl = np.ascontiguousarray(flags_in, np.int32).reshape(-1)
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        r = {"out": np.empty((n, 3), np.float32), "pdf": np.empty(n, np.float32), "f": np.empty((n, 3), np.float32),
+             "sample": np.empty((n, 2), np.float32), "flags": np.empty(n, np.int32), "valid": np.empty(n, np.int32)}
+        N.check(self.lib, self.lib.khp_debug_bsdf_sample(
+            self.ptr, n, self.KINDS_ALL if kinds_mask is None else kinds_mask, ip(ob), ip(mt), N.fptr(ri), N.fptr(nn),
+            N.fptr(sm), N.fptr(hu), ip(fl), N.fptr(r["out"]), N.fptr(r["pdf"]), N.fptr(r["f"]), N.fptr(r["sample"]),
+            ip(r["flags"]), ip(r["valid"])), "khp_debug_bsdf_sample")
+        return r
+
+    def debug_bsdf_eval(self, obj, mat, ray_in, normal, out):
+        """khp_debug_bsdf_eval on n items -> f (n, 3)."""
+        ob = np.ascontiguousarray(obj, np.int32).reshape(-1)
+        n = len(ob)
+        mt = np.ascontiguousarray(mat, np.int32).reshape(-1)
+        ri = np.ascontiguousarray(ray_in, np.float32).reshape(-1, 3)
+        nn = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        oo = np.ascontiguousarray(out, np.float32).reshape(-1, 3)
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        f = np.empty((n, 3), np.float32)
+        N.check(self.lib, self.lib.khp_debug_bsdf_eval(self.ptr, n, ip(ob), ip(mt), N.fptr(ri), N.fptr(nn), N.fptr(oo),
+                                                       N.fptr(f)), "khp_debug_bsdf_eval")
+        return f
+
+    def debug_light_dir(self, light, point, draws):
+        """khp_debug_light_dir on n items -> shadow ray origin, direction, attenuation."""
+        li = np.ascontiguousarray(light, np.int32).reshape(-1)
+        n = len(li)
+        p = np.ascontiguousarray(point, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(draws, np.float32).reshape(-1, 2)
+        r = {"o": np.empty((n, 3), np.float32), "d": np.empty((n, 3), np.float32), "att": np.empty(n, np.float32)}
+        N.check(self.lib, self.lib.khp_debug_light_dir(self.ptr, n, li.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                       N.fptr(p), N.fptr(u), N.fptr(r["o"]), N.fptr(r["d"]),
+                                                       N.fptr(r["att"])), "khp_debug_light_dir")
+        return r
+
+    def debug_light_isect(self, light, orig, direction):
+        """khp_debug_light_isect on n items -> hit, t, emitted colour."""
+        li = np.ascontiguousarray(light, np.int32).reshape(-1)
+        n = len(li)
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+        r = {"hit": np.empty(n, np.uint8), "t": np.empty(n, np.float32), "emit": np.empty((n, 3), np.float32)}
+        N.check(self.lib, self.lib.khp_debug_light_isect(self.ptr, n, li.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                         N.fptr(o), N.fptr(d),
+                                                         r["hit"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                                         N.fptr(r["t"]), N.fptr(r["emit"])), "khp_debug_light_isect")
+        return r
+
     def debug_queues(self):
         """The extension rays and the shadow rays (o, d, t_max) of bounce
         khp_ctx_params.dump_bounce of the last synchronous render."""

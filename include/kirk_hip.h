@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define KHP_ABI_VERSION 14
+#define KHP_ABI_VERSION 15
 
 typedef struct khp_ctx khp_ctx;
 
@@ -595,6 +595,47 @@ khp_status khp_debug_queue(khp_ctx* ctx, uint32_t* n, float* orig, float* dir);
 /* The same render's shadow rays of bounce b as k_shadow traces them (after the
  * zero-colour skip): origin, direction ([n][3]) and t_max ([n]). */
 khp_status khp_debug_shadow_queue(khp_ctx* ctx, uint32_t* n, float* orig, float* dir, float* tmax);
+/* ---- ABI 15: batch queries of the shading functions (test hooks) ------------
+ * Each runs the device functions the renderer calls on n independent items,
+ * one thread per item, so a test can pin them item by item (a float64
+ * reference, the oracle).  They add nothing to the render path.  All of them:
+ * n in [1, 2^20], no null array, a built scene; every object / material /
+ * light index is checked on the host -- KHP_EINVAL with khp_last_error naming
+ * the first bad item -- and nothing is launched for a refused call.
+ *
+ * khp_debug_surface: the closest hit of ray i (origin, direction [n][3]; the
+ * direction is normalised as KIRK::Ray does) and the surface there: t ([n],
+ * FLT_MAX on a miss), object id (-1), the shading normal [n][3], the hair
+ * frame U V W [n][9] (the cone's, or the fibre's for fur triangles; zero for
+ * plain triangles and on a miss) and the material index (-1). */
+khp_status khp_debug_surface(khp_ctx* ctx, uint32_t n, const float* orig, const float* dir, float* t,
+                             int32_t* object, float* normal, float* uvw, int32_t* material);
+/* BSDF::sample of material[i] (index into the scene's materials, untextured)
+ * at a synthetic hit on object[i] (its hair frame), for ray_in in[i], normal
+ * n[i], sample[i][2], the two hair draws hair[i][2] and the incoming flags.
+ * kinds_mask selects the compiled instance: (1 << KHP_BSDF_COUNT) - 1 for all
+ * kinds, or (1 << LAMBERTIAN_REFLECTION) | (1 << MARSCHNER_HAIR), the set the
+ * renderer compiles for fur-only scenes; any other mask, or an item whose
+ * material's kind is outside the mask, is KHP_EINVAL (the instance has that
+ * case compiled out).  Outputs: direction [n][3], pdf [n], f [n][3], the sample
+ * as written back [n][2], flags [n], valid [n] (0: the dot(in, n) == 0 early
+ * exit).  Outputs the BSDF does not write are the inputs / 0. */
+khp_status khp_debug_bsdf_sample(khp_ctx* ctx, uint32_t n, uint32_t kinds_mask, const int32_t* object,
+                                 const int32_t* material, const float* in, const float* normal,
+                                 const float* sample, const float* hair, const int32_t* flags_in, float* out_dir,
+                                 float* pdf, float* f, float* sample_out, int32_t* flags_out, int32_t* valid);
+/* BSDF::evaluateLight for the same kind of item and the direction out[i]: f [n][3]. */
+khp_status khp_debug_bsdf_eval(khp_ctx* ctx, uint32_t n, const int32_t* object, const int32_t* material,
+                               const float* in, const float* normal, const float* out, float* f);
+/* Light::calcLightdir (randomize = true) of light[i] from point[i] with the
+ * draws draws[i][2]: the shadow ray's origin and direction [n][3] and the
+ * attenuation [n]. */
+khp_status khp_debug_light_dir(khp_ctx* ctx, uint32_t n, const int32_t* light, const float* point,
+                               const float* draws, float* ray_orig, float* ray_dir, float* attenuation);
+/* Light::isIntersection and sampleLightSource of light[i] for ray i: hit [n]
+ * (0 / 1), t [n] (0 on a miss), the emitted colour [n][3]. */
+khp_status khp_debug_light_isect(khp_ctx* ctx, uint32_t n, const int32_t* light, const float* orig,
+                                 const float* dir, uint8_t* hit, float* t, float* emitted);
 /* ABI 13, test hook for the bounded device waits of a rank: builds
  * one RCCL-operation bracket (events `pre` / `post`, as around an ncclSend /
  * ncclRecv) on the context stream around a gate kernel that spins until

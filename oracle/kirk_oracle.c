@@ -2126,3 +2126,105 @@ int ko_bsdf_sample(ko_ctx* c, int hit_obj, const khp_material* mat, const float 
     f[0] = r.x; f[1] = r.y; f[2] = r.z;
     return flags;
 }
+
+/* ---- batch counterparts of the ABI 15 device queries (khp_debug_surface / _bsdf_* / _light) ---- */
+static void st3(float* d, v3 a) { d[0] = a.x; d[1] = a.y; d[2] = a.z; }
+
+/* BSDF::sample on n synthetic hits.  obj[i]: the object whose U/V/W frame is used,
+ * mat[i]: index into the scene's materials.  valid[i] = 0 on the early exit. */
+int ko_bsdf_sample_n(ko_ctx* c, uint32_t n, const int32_t* obj, const int32_t* mat, const float* in, const float* nrm,
+                     const float* sample, const float* hair, const int32_t* flags_in, float* out_dir, float* pdf,
+                     float* f, float* sample_out, int32_t* flags_out, int32_t* valid) {
+    if (!c) return KHP_EINVAL;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (obj[i] < 0 || (uint32_t)obj[i] >= c->n_obj || mat[i] < 0 || (uint32_t)mat[i] >= c->n_mats) return KHP_EINVAL;
+        shade_ctx_t s;
+        s.obj = &c->obj[obj[i]];
+        s.m = &c->mats[mat[i]];
+        s.n = ld3(nrm + 3 * (size_t)i);
+        float sm[2] = {sample[2 * (size_t)i], sample[2 * (size_t)i + 1]};
+        v3 out = V(0.0f, 0.0f, 0.0f);
+        float pd = 0.0f;
+        int flags = flags_in[i], ok = 0;
+        v3 r = bsdf_sample(&s, ld3(in + 3 * (size_t)i), s.n, sm, hair + 2 * (size_t)i, &out, &pd, &flags, &ok);
+        st3(out_dir + 3 * (size_t)i, out);
+        st3(f + 3 * (size_t)i, r);
+        pdf[i] = pd;
+        sample_out[2 * (size_t)i] = sm[0];
+        sample_out[2 * (size_t)i + 1] = sm[1];
+        flags_out[i] = flags;
+        valid[i] = ok;
+    }
+    return KHP_OK;
+}
+
+/* BSDF::evaluateLight on n synthetic hits. */
+int ko_bsdf_eval(ko_ctx* c, uint32_t n, const int32_t* obj, const int32_t* mat, const float* in, const float* nrm,
+                 const float* out, float* f) {
+    if (!c) return KHP_EINVAL;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (obj[i] < 0 || (uint32_t)obj[i] >= c->n_obj || mat[i] < 0 || (uint32_t)mat[i] >= c->n_mats) return KHP_EINVAL;
+        shade_ctx_t s;
+        s.obj = &c->obj[obj[i]];
+        s.m = &c->mats[mat[i]];
+        s.n = ld3(nrm + 3 * (size_t)i);
+        st3(f + 3 * (size_t)i, bsdf_eval(&s, ld3(in + 3 * (size_t)i), ld3(out + 3 * (size_t)i)));
+    }
+    return KHP_OK;
+}
+
+/* The surface at the closest hit of n rays: t, object (-1: miss, the rest zero),
+ * calcNormal, the hair frame U V W and the material index. */
+int ko_surface(ko_ctx* c, uint32_t n, const float* orig, const float* dir, float* t_out, int32_t* obj_out,
+               float* nrm, float* uvw, int32_t* mat) {
+    if (!c) return KHP_EINVAL;
+    for (uint32_t i = 0; i < n; ++i) {
+        ray_t r = make_ray(ld3(orig + 3 * (size_t)i), ld3(dir + 3 * (size_t)i));
+        hit_t h;
+        bvh_closest(c, &r, &h, NULL);
+        t_out[i] = h.lambda;
+        obj_out[i] = h.obj;
+        memset(nrm + 3 * (size_t)i, 0, 3 * sizeof(float));
+        memset(uvw + 9 * (size_t)i, 0, 9 * sizeof(float));
+        mat[i] = -1;
+        if (h.obj < 0) continue;
+        const obj_t* o = &c->obj[h.obj];
+        st3(nrm + 3 * (size_t)i, obj_normal(o, &r, &h));
+        st3(uvw + 9 * (size_t)i, o->u);
+        st3(uvw + 9 * (size_t)i + 3, o->v);
+        st3(uvw + 9 * (size_t)i + 6, o->w);
+        mat[i] = (int32_t)o->mat;
+    }
+    return KHP_OK;
+}
+
+/* calcLightdir (randomize = true) of light li[i] from point p[i] with draws u[i]. */
+int ko_light_dir(ko_ctx* c, uint32_t n, const int32_t* li, const float* p, const float* u, float* ro, float* rd,
+                 float* att) {
+    if (!c) return KHP_EINVAL;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (li[i] < 0 || (uint32_t)li[i] >= c->n_lights) return KHP_EINVAL;
+        float a = 0.0f;
+        ray_t r = light_dir(&c->lights[li[i]], ld3(p + 3 * (size_t)i), u[2 * (size_t)i], u[2 * (size_t)i + 1], &a);
+        st3(ro + 3 * (size_t)i, r.o);
+        st3(rd + 3 * (size_t)i, r.d);
+        att[i] = a;
+    }
+    return KHP_OK;
+}
+
+/* isIntersection + sampleLightSource of light li[i] for the ray (orig, dir); t is 0 on a miss. */
+int ko_light_isect(ko_ctx* c, uint32_t n, const int32_t* li, const float* orig, const float* dir, uint8_t* hit,
+                   float* t_out, float* emit) {
+    if (!c) return KHP_EINVAL;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (li[i] < 0 || (uint32_t)li[i] >= c->n_lights) return KHP_EINVAL;
+        ray_t r = make_ray(ld3(orig + 3 * (size_t)i), ld3(dir + 3 * (size_t)i));
+        float t = 0.0f;
+        const int h = light_isect(&c->lights[li[i]], &r, &t);
+        hit[i] = (uint8_t)h;
+        t_out[i] = h ? t : 0.0f;
+        st3(emit + 3 * (size_t)i, light_emit(&c->lights[li[i]], r.d));
+    }
+    return KHP_OK;
+}

@@ -97,6 +97,21 @@ int ko_bsdf_sample(ko_ctx* c, int hit_obj, const khp_material* mat, const float 
                    float sample_io[2], const float rng_hair[2], int flags_in,
                    float out_dir[3], float* pdf, float f[3]);
 
+/* Batch counterparts of the ABI 15 device queries (include/kirk_hip.h khp_debug_surface,
+ * khp_debug_bsdf_sample, khp_debug_bsdf_eval, khp_debug_light_dir, khp_debug_light_isect):
+ * the same arguments and outputs; an index out of range returns KHP_EINVAL. */
+int ko_bsdf_sample_n(ko_ctx* c, uint32_t n, const int32_t* obj, const int32_t* mat, const float* in, const float* nrm,
+                     const float* sample, const float* hair, const int32_t* flags_in, float* out_dir, float* pdf,
+                     float* f, float* sample_out, int32_t* flags_out, int32_t* valid);
+int ko_bsdf_eval(ko_ctx* c, uint32_t n, const int32_t* obj, const int32_t* mat, const float* in, const float* nrm,
+                 const float* out, float* f);
+int ko_surface(ko_ctx* c, uint32_t n, const float* orig, const float* dir, float* t_out, int32_t* obj_out,
+               float* nrm, float* uvw, int32_t* mat);
+int ko_light_dir(ko_ctx* c, uint32_t n, const int32_t* li, const float* p, const float* u, float* ro, float* rd,
+                 float* att);
+int ko_light_isect(ko_ctx* c, uint32_t n, const int32_t* li, const float* orig, const float* dir, uint8_t* hit,
+                   float* t_out, float* emit);
+
 /* Output stage (kirk_tonemap.c): Texture::setPixel byte conversion and
  * Tonemapper::map, sequential in KIRK's order. */
 void ko_tonemap_defaults(khp_tonemap* t);

@@ -72,6 +72,17 @@ def load():
         "ko_rand_u32": (c_uint32, [c_uint32, c_uint32, c_uint32, c_uint32]),
         "ko_bsdf_sample": (c_int, [c_void_p, c_int, c_void_p, P(c_float), P(c_float), P(c_float), P(c_float), c_int,
                                    P(c_float), P(c_float), P(c_float)]),
+        "ko_bsdf_sample_n": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_int32), P(c_float), P(c_float), P(c_float),
+                                     P(c_float), P(c_int32), P(c_float), P(c_float), P(c_float), P(c_float),
+                                     P(c_int32), P(c_int32)]),
+        "ko_bsdf_eval": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_int32), P(c_float), P(c_float), P(c_float),
+                                 P(c_float)]),
+        "ko_surface": (c_int, [c_void_p, c_uint32, P(c_float), P(c_float), P(c_float), P(c_int32), P(c_float),
+                               P(c_float), P(c_int32)]),
+        "ko_light_dir": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_float), P(c_float), P(c_float), P(c_float),
+                                 P(c_float)]),
+        "ko_light_isect": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_float), P(c_float), P(c_uint8), P(c_float),
+                                   P(c_float)]),
         "ko_to_rgba8": (None, [c_uint32, P(c_float), P(c_uint8)]),
         "ko_tonemap": (c_int, [c_uint32, c_uint32, P(c_float), c_void_p, P(c_float), P(c_float), P(c_float)]),
     }
@@ -213,6 +224,73 @@ class Oracle:
         fl = self.lib.ko_bsdf_sample(self.ptr, obj, ctypes.addressof(mat), _fp(ri), _fp(nn), _fp(s), _fp(hu),
                                      flags_in, _fp(out), ctypes.byref(pdf), _fp(f))
         return {"out": out, "pdf": pdf.value, "f": f, "flags": fl, "sample": s}
+
+    # ---- batch counterparts of the ABI 15 device queries (same names and keys as HipContext.debug_*) ----
+    def debug_surface(self, orig, direction):
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+        n = len(o)
+        r = {"t": np.empty(n, np.float32), "obj": np.empty(n, np.int32), "n": np.empty((n, 3), np.float32),
+             "uvw": np.empty((n, 3, 3), np.float32), "mat": np.empty(n, np.int32)}
+        rc = self.lib.ko_surface(self.ptr, n, _fp(o), _fp(d), _fp(r["t"]), _ip(r["obj"]), _fp(r["n"]), _fp(r["uvw"]),
+                                 _ip(r["mat"]))
+        if rc != 0:
+            raise ValueError(f"ko_surface failed ({rc})")
+        return r
+
+    def debug_bsdf_sample(self, obj, mat, ray_in, normal, sample, hair, flags_in, kinds_mask=None):
+        ob = np.ascontiguousarray(obj, np.int32).reshape(-1)
+        n = len(ob)
+        mt = np.ascontiguousarray(mat, np.int32).reshape(-1)
+        ri = np.ascontiguousarray(ray_in, np.float32).reshape(-1, 3)
+        nn = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        sm = np.ascontiguousarray(sample, np.float32).reshape(-1, 2)
+        hu = np.ascontiguousarray(hair, np.float32).reshape(-1, 2)
+        fl = np.ascontiguousarray(flags_in, np.int32).reshape(-1)
+        r = {"out": np.empty((n, 3), np.float32), "pdf": np.empty(n, np.float32), "f": np.empty((n, 3), np.float32),
+             "sample": np.empty((n, 2), np.float32), "flags": np.empty(n, np.int32), "valid": np.empty(n, np.int32)}
+        rc = self.lib.ko_bsdf_sample_n(self.ptr, n, _ip(ob), _ip(mt), _fp(ri), _fp(nn), _fp(sm), _fp(hu), _ip(fl),
+                                       _fp(r["out"]), _fp(r["pdf"]), _fp(r["f"]), _fp(r["sample"]), _ip(r["flags"]),
+                                       _ip(r["valid"]))
+        if rc != 0:
+            raise ValueError(f"ko_bsdf_sample_n failed ({rc})")
+        return r
+
+    def debug_bsdf_eval(self, obj, mat, ray_in, normal, out):
+        ob = np.ascontiguousarray(obj, np.int32).reshape(-1)
+        n = len(ob)
+        mt = np.ascontiguousarray(mat, np.int32).reshape(-1)
+        ri = np.ascontiguousarray(ray_in, np.float32).reshape(-1, 3)
+        nn = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        oo = np.ascontiguousarray(out, np.float32).reshape(-1, 3)
+        f = np.empty((n, 3), np.float32)
+        rc = self.lib.ko_bsdf_eval(self.ptr, n, _ip(ob), _ip(mt), _fp(ri), _fp(nn), _fp(oo), _fp(f))
+        if rc != 0:
+            raise ValueError(f"ko_bsdf_eval failed ({rc})")
+        return f
+
+    def debug_light_dir(self, light, point, draws):
+        li = np.ascontiguousarray(light, np.int32).reshape(-1)
+        n = len(li)
+        p = np.ascontiguousarray(point, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(draws, np.float32).reshape(-1, 2)
+        r = {"o": np.empty((n, 3), np.float32), "d": np.empty((n, 3), np.float32), "att": np.empty(n, np.float32)}
+        rc = self.lib.ko_light_dir(self.ptr, n, _ip(li), _fp(p), _fp(u), _fp(r["o"]), _fp(r["d"]), _fp(r["att"]))
+        if rc != 0:
+            raise ValueError(f"ko_light_dir failed ({rc})")
+        return r
+
+    def debug_light_isect(self, light, orig, direction):
+        li = np.ascontiguousarray(light, np.int32).reshape(-1)
+        n = len(li)
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+        r = {"hit": np.empty(n, np.uint8), "t": np.empty(n, np.float32), "emit": np.empty((n, 3), np.float32)}
+        rc = self.lib.ko_light_isect(self.ptr, n, _ip(li), _fp(o), _fp(d), r["hit"].ctypes.data_as(POINTER(c_uint8)),
+                                     _fp(r["t"]), _fp(r["emit"]))
+        if rc != 0:
+            raise ValueError(f"ko_light_isect failed ({rc})")
+        return r
 
 
 def to_rgba8(rgb: np.ndarray) -> np.ndarray:

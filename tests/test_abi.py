@@ -1,6 +1,7 @@
 """The C-ABI drop-in boundary (include/kirk_hip.h): library loads, exports what the
-header declares, registries mirror KIRK's factories, errors are loud.  CPU only:
-no compute calls need a GPU here (khp_create is checked to *fail* without one).
+header declares, registries mirror KIRK's factories, errors are loud.  CPU only (khp_create is
+checked to *fail* without a GPU), except the bad-argument cases of the ABI 15
+batch queries, which need a context (`gpu`).
 """
 import ctypes
 import os
@@ -8,6 +9,7 @@ import re
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from ba_pathtracing_fur_amd import native as N
@@ -150,3 +152,110 @@ def test_ctx_params_struct_matches_header():
                              "wide_from": 2, "path_kernel": 0, "ray_sort_from": 0, "lds_nodes": 0,
                              "render_ahead": 3, "path_from": 0}
     assert ctypes.sizeof(N.CtxParams) == 64  # 15 fields: 8 + 8 + 12 x 4 bytes
+
+
+# ---- ABI 15: the batch queries of the shading functions -------------------------------------
+def _debug_query_calls(n, null=None, obj=0, mat=0, light=0, mask=(1 << 11) - 1):
+    """(name, callable(lib, ctx)) for each of the five queries on n items (arrays of at most 4: a
+    larger n is to be refused before anything is read); `null` names one argument to omit."""
+    f = lambda *shape: np.zeros(shape, np.float32)
+    i = lambda v=0: np.full(m, v, np.int32)
+    keep = []
+
+    def a(name, arr):
+        if name == null:
+            return None
+        keep.append(arr)
+        return arr.ctypes.data_as(ctypes.c_void_p)
+
+    m = min(max(n, 1), 4)
+    d = np.tile(np.float32([0, 0, -1]), (m, 1))
+    up = np.tile(np.float32([0, 0, 1]), (m, 1))
+    return [
+        ("khp_debug_surface", lambda lib, c: lib.khp_debug_surface(
+            c, n, *(ctypes.cast(a(k, v), ctypes.POINTER(t)) for k, v, t in (
+                ("orig", f(m, 3), ctypes.c_float), ("dir", d, ctypes.c_float), ("t", f(m), ctypes.c_float),
+                ("object", i(), ctypes.c_int32), ("normal", f(m, 3), ctypes.c_float), ("uvw", f(m, 9), ctypes.c_float),
+                ("material", i(), ctypes.c_int32))))),
+        ("khp_debug_bsdf_sample", lambda lib, c: lib.khp_debug_bsdf_sample(
+            c, n, mask, *(ctypes.cast(a(k, v), ctypes.POINTER(t)) for k, v, t in (
+                ("object", i(obj), ctypes.c_int32), ("material", i(mat), ctypes.c_int32), ("in", up, ctypes.c_float),
+                ("normal", up, ctypes.c_float), ("sample", f(m, 2), ctypes.c_float), ("hair", f(m, 2), ctypes.c_float),
+                ("flags_in", i(), ctypes.c_int32), ("out_dir", f(m, 3), ctypes.c_float), ("pdf", f(m), ctypes.c_float),
+                ("f", f(m, 3), ctypes.c_float), ("sample_out", f(m, 2), ctypes.c_float),
+                ("flags_out", i(), ctypes.c_int32), ("valid", i(), ctypes.c_int32))))),
+        ("khp_debug_bsdf_eval", lambda lib, c: lib.khp_debug_bsdf_eval(
+            c, n, *(ctypes.cast(a(k, v), ctypes.POINTER(t)) for k, v, t in (
+                ("object", i(obj), ctypes.c_int32), ("material", i(mat), ctypes.c_int32), ("in", up, ctypes.c_float),
+                ("normal", up, ctypes.c_float), ("out", up, ctypes.c_float), ("f", f(m, 3), ctypes.c_float))))),
+        ("khp_debug_light_dir", lambda lib, c: lib.khp_debug_light_dir(
+            c, n, *(ctypes.cast(a(k, v), ctypes.POINTER(t)) for k, v, t in (
+                ("light", i(light), ctypes.c_int32), ("point", f(m, 3), ctypes.c_float), ("draws", f(m, 2), ctypes.c_float),
+                ("ray_orig", f(m, 3), ctypes.c_float), ("ray_dir", f(m, 3), ctypes.c_float),
+                ("attenuation", f(m), ctypes.c_float))))),
+        ("khp_debug_light_isect", lambda lib, c: lib.khp_debug_light_isect(
+            c, n, *(ctypes.cast(a(k, v), ctypes.POINTER(t)) for k, v, t in (
+                ("light", i(light), ctypes.c_int32), ("orig", f(m, 3), ctypes.c_float), ("dir", d, ctypes.c_float),
+                ("hit", np.zeros(m, np.uint8), ctypes.c_uint8), ("t", f(m), ctypes.c_float),
+                ("emitted", f(m, 3), ctypes.c_float))))),
+    ]
+
+
+def test_debug_queries_need_a_context():
+    lib = N.load_library()
+    for name, call in _debug_query_calls(4):
+        assert call(lib, None) == N.KHP_EINVAL, name
+        assert b"null" in lib.khp_last_error(), name
+
+
+@pytest.mark.gpu
+def test_debug_queries_refuse_bad_arguments(hip_ctx):
+    """Every argument of the ABI 15 queries is checked on the host: nothing out of range reaches a kernel."""
+    from ba_pathtracing_fur_amd.pathtracer import HipContext
+    lib = N.load_library()
+    err = lambda: lib.khp_last_error().decode()
+    fresh = HipContext(0)                      # no scene yet
+    try:
+        for name, call in _debug_query_calls(4):
+            assert call(lib, fresh.ptr) == N.KHP_ENOTREADY, name
+            assert "khp_set_scene" in err(), name
+        fresh.set_scene(S.config1(8, 8))       # a scene, but no tree
+        for name, call in _debug_query_calls(4):
+            assert call(lib, fresh.ptr) == N.KHP_ENOTREADY, name
+            assert "khp_build_accel" in err(), name
+    finally:
+        fresh.close()
+    sd = S.config2(8, 8, n_strands=20)         # 4 materials (3 Lambert + Marschner), 1 light
+    hip_ctx.set_scene(sd)
+    hip_ctx.build_accel()
+    c = hip_ctx.ptr
+    for name, call in _debug_query_calls(4):
+        assert call(lib, c) == N.KHP_OK, (name, err())
+    for n in (0, (1 << 20) + 1, 0xFFFFFFFF):
+        for name, call in _debug_query_calls(n):
+            assert call(lib, c) == N.KHP_EINVAL and "n must be" in err(), (name, n)
+    args = {"khp_debug_surface": ["orig", "dir", "t", "object", "normal", "uvw", "material"],
+            "khp_debug_bsdf_sample": ["object", "material", "in", "normal", "sample", "hair", "flags_in", "out_dir", "pdf",
+                                      "f", "sample_out", "flags_out", "valid"],
+            "khp_debug_bsdf_eval": ["object", "material", "in", "normal", "out", "f"],
+            "khp_debug_light_dir": ["light", "point", "draws", "ray_orig", "ray_dir", "attenuation"],
+            "khp_debug_light_isect": ["light", "orig", "dir", "hit", "t", "emitted"]}
+    for k, (name, _) in enumerate(_debug_query_calls(4)):
+        for arg in args[name]:
+            call = _debug_query_calls(4, null=arg)[k][1]
+            assert call(lib, c) == N.KHP_EINVAL and "null" in err(), (name, arg)
+    bsdf = lambda **kw: [x for x in _debug_query_calls(4, **kw) if "bsdf" in x[0]]
+    light = lambda **kw: [x for x in _debug_query_calls(4, **kw) if "light" in x[0]]
+    for bad in (-1, sd.n_objects, 1 << 30):
+        for name, call in bsdf(obj=bad):
+            assert call(lib, c) == N.KHP_EINVAL and "object" in err(), (name, bad)
+    for bad in (-1, len(sd.materials), 1 << 30):
+        for name, call in bsdf(mat=bad):
+            assert call(lib, c) == N.KHP_EINVAL and "material" in err(), (name, bad)
+    for bad in (-1, len(sd.lights), 1 << 30):
+        for name, call in light(light=bad):
+            assert call(lib, c) == N.KHP_EINVAL and "light" in err(), (name, bad)
+    # the fur instance accepts Lambert (material 0) and Marschner (3) only; any other mask is refused
+    fur = (1 << 0) | (1 << 9)
+    assert bsdf(mask=fur, mat=3)[0][1](lib, c) == N.KHP_OK
+    assert bsdf(mask=0x7)[0][1](lib, c) == N.KHP_EINVAL and "kinds_mask" in err()

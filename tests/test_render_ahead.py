@@ -137,7 +137,7 @@ def test_changes_between_calls_drop_the_ahead_work():
 
 
 def test_render_ahead_off_and_validation(hip_ctx):
-    """render_ahead 0 renders the same frames with nothing ahead; values > 1 are refused."""
+    """render_ahead 0 renders the same frames with nothing ahead; values above 3 (here 4) are refused."""
     w, h, depth = 48, 32, 5
     sd = S.config2(w, h, n_strands=1000)
     hip_ctx.set_scene(sd)
