@@ -1,8 +1,9 @@
-// debug_query.h -- ABI 15 batch queries of the shading functions (test hooks,
+// debug_query.h -- ABI 15 / 16 batch queries of the shading functions (test hooks,
 // included by render.hip next to khp_debug_queue).  Each kernel runs one item
 // per thread in a grid-stride loop and calls the __device__ functions the
 // renderer calls -- trace_closest, surface_at, bsdf_sample<KINDS>, bsdf_eval,
-// light_dir, light_isect, light_emit -- so a test can compare them item by item
+// light_dir, light_isect, light_emit, and (ABI 16) bsdf_sample's KINDS_LOBES
+// instance, hair_lobes.h -- so a test can compare them item by item
 // with the oracle and with a float64 reference.  Every index is checked on the
 // host before a launch; the kernels read nothing the host has not validated.
 #pragma once
@@ -86,6 +87,35 @@ __global__ __launch_bounds__(DBG_BLOCK) void k_dbg_bsdf_sample(DevScene S, uint3
         bool ok = false;
         const v3 r = bsdf_sample<KINDS>(s, ld3(in + 3 * (size_t)i), s.n, sm, hair[2 * (size_t)i],
                                         hair[2 * (size_t)i + 1], out, pd, flags, ok);
+        st3(out_dir + 3 * (size_t)i, out);
+        st3(f + 3 * (size_t)i, r);
+        pdf[i] = pd;
+        sample_out[2 * (size_t)i] = sm[0];
+        sample_out[2 * (size_t)i + 1] = sm[1];
+        flags_out[i] = flags;
+        valid[i] = ok ? 1 : 0;
+    }
+}
+
+// ABI 16: bsdf_sample of a KINDS_LOBES instance (hair_lobes.h) with the lobe set and draw of the call.
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_hair_sample(DevScene S, uint32_t n, uint32_t lobes, const uint32_t* slot,
+                                                               const int32_t* mat, const float* in, const float* nrm,
+                                                               const float* hair, const float* lobe_u,
+                                                               const int32_t* flags_in, float* out_dir, float* pdf,
+                                                               float* f, float* sample_out, int32_t* flags_out,
+                                                               int32_t* valid) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        ShadeCtx s;
+        dbg_frame(S, slot[i], s);
+        s.m = &S.mats[mat[i]];
+        s.n = ld3(nrm + 3 * (size_t)i);
+        float sm[2] = {0.0f, 0.0f};
+        v3 out = mk(0.0f, 0.0f, 0.0f);
+        float pd = 0.0f;
+        int flags = flags_in[i];
+        bool ok = false;
+        const v3 r = bsdf_sample<KINDS_FUR | KINDS_LOBES>(s, ld3(in + 3 * (size_t)i), s.n, sm, hair[2 * (size_t)i],
+                                                          hair[2 * (size_t)i + 1], out, pd, flags, ok, lobe_u[i], lobes);
         st3(out_dir + 3 * (size_t)i, out);
         st3(f + 3 * (size_t)i, r);
         pdf[i] = pd;
@@ -248,6 +278,50 @@ extern "C" khp_status khp_debug_bsdf_sample(khp_ctx* c, uint32_t n, uint32_t kin
                            sl.as<uint32_t>(), mt.as<int32_t>(), di.as<float>(), dn.as<float>(), ds.as<float>(),
                            dh.as<float>(), dfl.as<int32_t>(), od.as<float>(), op.as<float>(), of.as<float>(),
                            os.as<float>(), ofl.as<int32_t>(), ov.as<int32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_dir, od.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(pdf, op.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(f, of.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(sample_out, os.p, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(flags_out, ofl.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(valid, ov.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the BSDF queries"));
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_debug_hair_sample(khp_ctx* c, uint32_t n, uint32_t lobes, const int32_t* obj,
+                                            const int32_t* mat, const float* in, const float* normal,
+                                            const float* hair, const float* lobe_u, const int32_t* flags_in,
+                                            float* out_dir, float* pdf, float* f, float* sample_out,
+                                            int32_t* flags_out, int32_t* valid) {
+    KHPCHK(dbg_enter(c, n, obj && mat && in && normal && hair && lobe_u && flags_in && out_dir && pdf && f &&
+                               sample_out && flags_out && valid));
+    if (lobes == 0u || (lobes & ~HAIR_LOBE_ALL))
+        return fail(KHP_EINVAL, "lobes must be a non-empty set of KHP_HAIR_LOBE_R, _TT, _TRT");
+    std::vector<uint32_t> slots;
+    KHPCHK(dbg_bsdf_items(c, n, obj, mat, KINDS_ALL, slots));
+    for (uint32_t i = 0; i < n; ++i)
+        if (c->hs.mats[mat[i]].bsdf != KHP_BSDF_MARSCHNER_HAIR)
+            return fail(KHP_EINVAL, "item " + std::to_string(i) + ": material " + std::to_string(mat[i]) +
+                                        " is not KHP_BSDF_MARSCHNER_HAIR");
+    DevMem sl, mt, di, dn, dh, du, dfl, od, op, of, os, ofl, ov;
+    HIPCHK(upload(sl, slots.data(), (size_t)n, c->stream));
+    HIPCHK(upload(mt, mat, (size_t)n, c->stream));
+    HIPCHK(upload(di, in, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(dn, normal, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(dh, hair, 2 * (size_t)n, c->stream));
+    HIPCHK(upload(du, lobe_u, (size_t)n, c->stream));
+    HIPCHK(upload(dfl, flags_in, (size_t)n, c->stream));
+    HIPCHK(od.ensure(12 * (size_t)n));
+    HIPCHK(op.ensure(4 * (size_t)n));
+    HIPCHK(of.ensure(12 * (size_t)n));
+    HIPCHK(os.ensure(8 * (size_t)n));
+    HIPCHK(ofl.ensure(4 * (size_t)n));
+    HIPCHK(ov.ensure(4 * (size_t)n));
+    hipLaunchKernelGGL(k_dbg_hair_sample, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n, lobes,
+                       sl.as<uint32_t>(), mt.as<int32_t>(), di.as<float>(), dn.as<float>(), dh.as<float>(),
+                       du.as<float>(), dfl.as<int32_t>(), od.as<float>(), op.as<float>(), of.as<float>(),
+                       os.as<float>(), ofl.as<int32_t>(), ov.as<int32_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_dir, od.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(pdf, op.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));

@@ -46,6 +46,7 @@ struct DevScene {
     // the refs between them rewritten to TOP_REF | index, and the root's ref in that form
     const float4* __restrict__ top;
     int32_t top_root;
+    uint32_t hair_lobes;   // khp_set_hair_lobes: KHP_HAIR_LOBE_* bits, read by KINDS_LOBES instances only
 };
 
 // ---- textures (ABI 6) -------------------------------------------------------------------
@@ -520,6 +521,19 @@ __device__ __forceinline__ v3 hair_r(const ShadeCtx& s, v3 in, v3 n, float sampl
     }
 }
 
+}  // namespace khp
+
+#include "hair_lobes.h"   // Marschner's TT / TRT paths (hair_lobes), behind KINDS_LOBES
+
+namespace khp {
+
+// A spare bit of the KINDS sets below: the instance traces Marschner's TT and TRT
+// paths (khp_set_hair_lobes).  The all-ones default of KINDS predates the bit and
+// means every BSDF kind with the R lobe only.
+constexpr uint32_t KINDS_LOBES = 1u << 31;
+template <uint32_t KINDS>
+constexpr bool kinds_lobes = KINDS != 0xFFFFFFFFu && (KINDS & KINDS_LOBES) != 0u;
+
 // BSDF::sample (Bsdf.cpp:179-184) + localSample dispatch; valid=false on the
 // `dot(ray_in, normal) == 0` early exit.
 // Inlined into k_shade: measured 2.02 -> 1.66 ms per frame against a real call
@@ -528,10 +542,12 @@ __device__ __forceinline__ v3 hair_r(const ShadeCtx& s, v3 in, v3 n, float sampl
 // KINDS: the BSDF kinds the scene's materials use (bit k = khp_bsdf_kind k), a
 // compile-time set: the other cases are compiled out (their registers with
 // them).  The host instantiates a kernel whose set covers every material.
+// lobe_u, lobes: the lobe draw and the enabled lobes, read by KINDS_LOBES instances only.
 template <uint32_t KINDS = 0xFFFFFFFFu>
 __device__ __forceinline__
 v3 bsdf_sample(const ShadeCtx& s, v3 in, v3 n, float sample[2], float h0, float h1, v3& out,
-                                       float& pdf, int& flags, bool& valid) {
+                                       float& pdf, int& flags, bool& valid, float lobe_u = 0.0f,
+                                       uint32_t lobes = HAIR_LOBE_R) {
     v3 zero = mk(0.0f, 0.0f, 0.0f);
     valid = true;
     if (dot(in, n) == 0.0f) {
@@ -658,7 +674,8 @@ v3 bsdf_sample(const ShadeCtx& s, v3 in, v3 n, float sample[2], float h0, float 
             return vol / fabsf(dot(out, n));
         case KHP_BSDF_MARSCHNER_HAIR:
             if constexpr (!(KINDS & (1u << KHP_BSDF_MARSCHNER_HAIR))) __builtin_unreachable();
-            return hair_r<false>(s, in, n, sample, h0, h1, out, pdf, flags);
+            if constexpr (kinds_lobes<KINDS>) return hair_lobes(s, in, n, sample, h0, h1, lobe_u, lobes, out, pdf, flags);
+            else return hair_r<false>(s, in, n, sample, h0, h1, out, pdf, flags);
         case KHP_BSDF_DEON_HAIR:
             if constexpr (!(KINDS & (1u << KHP_BSDF_DEON_HAIR))) __builtin_unreachable();
             return hair_r<true>(s, in, n, sample, h0, h1, out, pdf, flags);

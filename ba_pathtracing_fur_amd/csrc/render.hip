@@ -1198,7 +1198,9 @@ __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_s
                     v3 out;
                     float pdf = 0.0f;
                     bool valid;
-                    v3 refl = bsdf_sample<KINDS>(s, counter, nrm, smp, h0, h1, out, pdf, flags, valid);
+                    float hl = 0.0f;   // the lobe draw of hair_lobes.h (lobe instances only)
+                    if constexpr (kinds_lobes<KINDS>) hl = draw_u01(key, dim_of(bounce, P_HAIR_LOBE));
+                    v3 refl = bsdf_sample<KINDS>(s, counter, nrm, smp, h0, h1, out, pdf, flags, valid, hl, S.hair_lobes);
                     v3 off = out * 1e-4f;
                     if (!(flags & F_SPECULAR)) off = faceforward(-(nrm * 1e-4f), nrm, out);
                     nr = make_ray(loc + off, out);
@@ -1740,7 +1742,9 @@ __device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, floa
             v3 out;
             float pdf = 0.0f;
             bool valid;
-            v3 refl = bsdf_sample<KINDS>(s, counter, nrm, smp, h0, h1, out, pdf, flags, valid);
+            float hl = 0.0f;   // the lobe draw of hair_lobes.h (lobe instances only)
+            if constexpr (kinds_lobes<KINDS>) hl = draw_u01(key, dim_of(bounce, P_HAIR_LOBE));
+            v3 refl = bsdf_sample<KINDS>(s, counter, nrm, smp, h0, h1, out, pdf, flags, valid, hl, S.hair_lobes);
             v3 off = out * 1e-4f;
             if (!(flags & F_SPECULAR)) off = faceforward(-(nrm * 1e-4f), nrm, out);
             o.nr = make_ray(loc + off, out);
@@ -2208,8 +2212,22 @@ static void launch_path_k(int grid, hipStream_t s, const DevScene& S, const Wave
     if (A.on) hipLaunchKernelGGL((k_path<TEX, WIDE, K, true>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
     else hipLaunchKernelGGL((k_path<TEX, WIDE, K, false>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
 }
-static void launch_path(bool tex, bool wide, bool fur, int grid, hipStream_t s, const DevScene& S, const Wave& W,
-                        SpillArea sp, const PathLanes& L, const Ahead& A, bool qs = false) {
+// lobes: the instances with Marschner's TT / TRT paths compiled in (khp_set_hair_lobes)
+static void launch_path(bool tex, bool wide, bool fur, bool lobes, int grid, hipStream_t s, const DevScene& S,
+                        const Wave& W, SpillArea sp, const PathLanes& L, const Ahead& A, bool qs = false) {
+    if (lobes) {
+        if (tex) {
+            if (wide) launch_path_k<true, true, KINDS_ALL | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
+            else launch_path_k<true, false, KINDS_ALL | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
+        } else if (fur) {
+            if (wide) launch_path_k<false, true, KINDS_FUR | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
+            else launch_path_k<false, false, KINDS_FUR | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
+        } else {
+            if (wide) launch_path_k<false, true, KINDS_ALL | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
+            else launch_path_k<false, false, KINDS_ALL | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
+        }
+        return;
+    }
     if (tex) {
         if (wide) launch_path_k<true, true, KINDS_ALL>(grid, s, S, W, sp, L, A, qs);
         else launch_path_k<true, false, KINDS_ALL>(grid, s, S, W, sp, L, A, qs);
@@ -2700,6 +2718,7 @@ struct khp_ctx {
     int grid_sh_w = 0;     // k_shadow on the two-level records
     int grid_path = 0, grid_path_w = 0;   // k_path (64-B / two-level records)
     uint32_t bsdf_kinds = 0;              // the BSDF kinds the scene's materials use (bit per khp_bsdf_kind)
+    // (khp_set_hair_lobes keeps its mask in S.hair_lobes: the scene build leaves it alone)
     int grid_ext_max = 0;  // the k_extend spill columns are sized for the largest grid
     khp_stats st{};
     // rccl gather: pixel lists cached per (W, H, tile, nranks, rank, root)
@@ -3000,6 +3019,8 @@ extern "C" khp_status khp_get_bdpt(khp_ctx* c, khp_bdpt_params* out) {
 
 extern "C" khp_status khp_set_bdpt(khp_ctx* c, const khp_bdpt_params* p) {
     if (!c || !p) return fail(KHP_EINVAL, "null argument");
+    if (p->enabled && c->S.hair_lobes != HAIR_LOBE_R)
+        return fail(KHP_EUNSUPPORTED, "the light-path variant traces the R lobe only: khp_set_hair_lobes(R) first");
     if (p->enabled && (p->light_paths < 1 || p->light_paths > 65536))
         return fail(KHP_EINVAL, "light_paths must be 1..65536");
     if (p->enabled && (p->vertices < 1 || p->vertices > 16)) return fail(KHP_EINVAL, "vertices must be 1..16");
@@ -3008,6 +3029,32 @@ extern "C" khp_status khp_set_bdpt(khp_ctx* c, const khp_bdpt_params* p) {
     khp_status dr = drain(c);  // frames in flight finish with the estimator they started with
     if (dr != KHP_OK) return dr;
     c->bd = *p;
+    ++c->gen;
+    return KHP_OK;
+}
+
+extern "C" void khp_hair_lobes_defaults(khp_hair_lobes* out) {
+    if (!out) return;
+    *out = khp_hair_lobes{};
+    out->lobes = KHP_HAIR_LOBE_R;   // KIRK as shipped: `int p = 0;` (Bsdf.cpp:669)
+}
+
+extern "C" khp_status khp_get_hair_lobes(khp_ctx* c, khp_hair_lobes* out) {
+    if (!c || !out) return fail(KHP_EINVAL, "null argument");
+    *out = khp_hair_lobes{c->S.hair_lobes, 0u};
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_set_hair_lobes(khp_ctx* c, const khp_hair_lobes* p) {
+    if (!c || !p) return fail(KHP_EINVAL, "null argument");
+    if (p->lobes == 0u || (p->lobes & ~HAIR_LOBE_ALL)) return fail(KHP_EINVAL, "lobes must be a non-empty set of KHP_HAIR_LOBE_R, _TT, _TRT");
+    if (p->reserved != 0u) return fail(KHP_EINVAL, "reserved must be 0");
+    if (p->lobes != KHP_HAIR_LOBE_R && c->bd.enabled)
+        return fail(KHP_EUNSUPPORTED, "the light-path variant traces the R lobe only: disable khp_set_bdpt first");
+    HIPCHK(hipSetDevice(c->device));
+    khp_status dr = drain(c);  // frames in flight finish with the lobes they started with
+    if (dr != KHP_OK) return dr;
+    c->S.hair_lobes = p->lobes;
     ++c->gen;
     return KHP_OK;
 }
@@ -3035,6 +3082,7 @@ extern "C" khp_status khp_create(khp_ctx** out, int device, uint32_t flags) {
     c->flags = flags;
     khp_ctx_params_defaults(&c->prm);
     khp_bdpt_params_defaults(&c->bd);
+    c->S.hair_lobes = HAIR_LOBE_R;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -4023,6 +4071,7 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
         sp_path = SpillArea{w.pspill.as<int4>(), (uint32_t)lanes};
     }
     const int grid_path = std::max(1, ((path_wide || hyb_wide) ? c->grid_path_w : c->grid_path) / G);
+    const bool lobes_on = c->S.hair_lobes != HAIR_LOBE_R;   // khp_set_hair_lobes: the KINDS_LOBES instances
     if (stats) {
         const size_t chunks = (size_t)((P_all + P_chunk - 1) / P_chunk) * ((p->spp + S_chunk - 1) / S_chunk);
         HIPCHK(c->snap.ensure(std::max<size_t>(1, chunks * p->depth) * sizeof(Counters)));
@@ -4113,8 +4162,8 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
                 HIPCHK(hipMemsetAsync(reinterpret_cast<char*>(Wv.cnt) + offsetof(Counters, fetch_ext), 0,
                                       sizeof(Counters::fetch_ext), sA));
                 timed(c, f, 3, true, sA);
-                launch_path(c->S.textured != 0, path_wide, (c->bsdf_kinds & ~KINDS_FUR) == 0u, grid_path, sA, c->S, Wv,
-                            sp_path, PL, AH);
+                launch_path(c->S.textured != 0, path_wide, (c->bsdf_kinds & ~KINDS_FUR) == 0u, lobes_on, grid_path, sA,
+                            c->S, Wv, sp_path, PL, AH);
                 HIPCHK(hipGetLastError());
                 if (ahead) ahead_commit(c, p, call_paths);
                 timed(c, f, 3, false, sA);
@@ -4196,7 +4245,16 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
                     hipLaunchKernelGGL(k_hit_class, dim3(c->grid_shade), dim3(256), 0, sA, c->S, Wb, cur);
                     hipLaunchKernelGGL(k_hit_scatter, dim3(c->grid_shade), dim3(256), 0, sA, Wb, cur);
                 }
-                if (c->S.textured && bdm)
+                if (lobes_on && c->S.textured)   // TT / TRT compiled in (never with the light-path variant)
+                    hipLaunchKernelGGL((k_shade<true, false, KINDS_ALL | KINDS_LOBES>), dim3(c->grid_shade), dim3(shade_block<true, false>()), 0, sA,
+                                       c->S, Wb, cur, b);
+                else if (lobes_on && (c->bsdf_kinds & ~KINDS_FUR) == 0u)
+                    hipLaunchKernelGGL((k_shade<false, false, KINDS_FUR | KINDS_LOBES>), dim3(c->grid_shade), dim3(shade_block<false, false>()), 0,
+                                       sA, c->S, Wb, cur, b);
+                else if (lobes_on)
+                    hipLaunchKernelGGL((k_shade<false, false, KINDS_ALL | KINDS_LOBES>), dim3(c->grid_shade), dim3(shade_block<false, false>()), 0,
+                                       sA, c->S, Wb, cur, b);
+                else if (c->S.textured && bdm)
                     hipLaunchKernelGGL((k_shade<true, true>), dim3(c->grid_shade_bd), dim3(shade_block<true, true>()), 0, sA, c->S, Wb, cur, b);
                 else if (c->S.textured)
                     hipLaunchKernelGGL((k_shade<true, false>), dim3(c->grid_shade), dim3(shade_block<true, false>()), 0, sA, c->S, Wb, cur, b);
@@ -4306,7 +4364,7 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
                 prepped = false;
                 c->cur_bounce = (int)hyb_from;
                 timed(c, f, 3, true, sA);
-                launch_path(c->S.textured != 0, hyb_wide, (c->bsdf_kinds & ~KINDS_FUR) == 0u, grid_path, sA, c->S, Wq,
+                launch_path(c->S.textured != 0, hyb_wide, (c->bsdf_kinds & ~KINDS_FUR) == 0u, lobes_on, grid_path, sA, c->S, Wq,
                             sp_path, PL, Ahead{}, true);
                 HIPCHK(hipGetLastError());
                 timed(c, f, 3, false, sA);

@@ -141,6 +141,14 @@ class BdptParams(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+HAIR_LOBE_R, HAIR_LOBE_TT, HAIR_LOBE_TRT = 1, 2, 4
+
+
+class HairLobes(ctypes.Structure):
+    """khp_hair_lobes (ABI 16, 8 bytes): the enabled lobes of Marschner's fibre model."""
+    _fields_ = [("lobes", c_uint32), ("reserved", c_uint32)]
+
+
 class Tonemap(ctypes.Structure):
     """khp_tonemap: KIRK::Tonemapper's parameters (Utils/Tonemapping.h:22-33)."""
     _fields_ = [("exposure", c_float), ("bias", c_float), ("gamma", c_float), ("contrast", c_float),
@@ -195,10 +203,11 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_read_rgba8_async", "khp_snapshot_wait", "khp_comm_init_local", "khp_comm_set_timeout",
             "khp_tonemap_log_sum", "khp_set_camera", "khp_debug_comm_wait", "khp_fur_params_defaults",
             "khp_fur_count", "khp_gen_fur", "khp_gen_fur_device", "khp_debug_surface", "khp_debug_bsdf_sample",
-            "khp_debug_bsdf_eval", "khp_debug_light_dir", "khp_debug_light_isect"]
+            "khp_debug_bsdf_eval", "khp_debug_light_dir", "khp_debug_light_isect", "khp_hair_lobes_defaults",
+            "khp_set_hair_lobes", "khp_get_hair_lobes", "khp_debug_hair_sample"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _lib = None
 
@@ -295,6 +304,12 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
                                           P(c_float), P(c_int32), P(c_int32)]),
         "khp_debug_bsdf_eval": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_int32), P(c_float), P(c_float),
                                         P(c_float), P(c_float)]),
+        "khp_hair_lobes_defaults": (None, [P(HairLobes)]),
+        "khp_set_hair_lobes": (c_int, [c_void_p, P(HairLobes)]),
+        "khp_get_hair_lobes": (c_int, [c_void_p, P(HairLobes)]),
+        "khp_debug_hair_sample": (c_int, [c_void_p, c_uint32, c_uint32, P(c_int32), P(c_int32), P(c_float), P(c_float),
+                                          P(c_float), P(c_float), P(c_int32), P(c_float), P(c_float), P(c_float),
+                                          P(c_float), P(c_int32), P(c_int32)]),
         "khp_debug_light_dir": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_float), P(c_float), P(c_float),
                                         P(c_float), P(c_float)]),
         "khp_debug_light_isect": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_float), P(c_float), P(c_uint8),

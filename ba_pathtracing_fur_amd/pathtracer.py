@@ -216,6 +216,22 @@ class HipContext:
         N.check(self.lib, self.lib.khp_set_bdpt(self.ptr, ctypes.byref(prm)), "khp_set_bdpt")
         return old
 
+    def set_hair_lobes(self, lobes: int) -> int:
+        """khp_set_hair_lobes (ABI 16): the lobes of Marschner's fibre model the next renders
+        trace, a non-empty set of HAIR_LOBE_R / _TT / _TRT (the default, R, is KIRK as
+        shipped); nothing is rebuilt.  Returns the previous set."""
+        old = self.hair_lobes
+        prm = N.HairLobes(int(lobes), 0)
+        N.check(self.lib, self.lib.khp_set_hair_lobes(self.ptr, ctypes.byref(prm)), "khp_set_hair_lobes")
+        return old
+
+    @property
+    def hair_lobes(self) -> int:
+        """khp_get_hair_lobes: the enabled lobes (HAIR_LOBE_* bits)."""
+        prm = N.HairLobes()
+        N.check(self.lib, self.lib.khp_get_hair_lobes(self.ptr, ctypes.byref(prm)), "khp_get_hair_lobes")
+        return int(prm.lobes)
+
     def render(self, width, height, spp, depth, seed=0x4B49524B, first_sample=0, tile_size=64, tile_rank=0,
                tile_nranks=1, out: np.ndarray | None = None, readback=True, stats=False,
                async_: bool = False) -> np.ndarray | None:
@@ -354,6 +370,26 @@ class HipContext:
             self.ptr, n, self.KINDS_ALL if kinds_mask is None else kinds_mask, ip(ob), ip(mt), N.fptr(ri), N.fptr(nn),
             N.fptr(sm), N.fptr(hu), ip(fl), N.fptr(r["out"]), N.fptr(r["pdf"]), N.fptr(r["f"]), N.fptr(r["sample"]),
             ip(r["flags"]), ip(r["valid"])), "khp_debug_bsdf_sample")
+        return r
+
+    def debug_hair_sample(self, lobes, obj, mat, ray_in, normal, hair, lobe_u, flags_in):
+        """khp_debug_hair_sample (ABI 16) on n items of Marschner materials: the three-call
+        TT / TRT state machine with the lobe set `lobes` (not the context's setting)."""
+        ob = np.ascontiguousarray(obj, np.int32).reshape(-1)
+        n = len(ob)
+        mt = np.ascontiguousarray(mat, np.int32).reshape(-1)
+        ri = np.ascontiguousarray(ray_in, np.float32).reshape(-1, 3)
+        nn = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        hu = np.ascontiguousarray(hair, np.float32).reshape(-1, 2)
+        lu = np.ascontiguousarray(lobe_u, np.float32).reshape(-1)
+        fl = np.ascontiguousarray(flags_in, np.int32).reshape(-1)
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        r = {"out": np.empty((n, 3), np.float32), "pdf": np.empty(n, np.float32), "f": np.empty((n, 3), np.float32),
+             "sample": np.empty((n, 2), np.float32), "flags": np.empty(n, np.int32), "valid": np.empty(n, np.int32)}
+        N.check(self.lib, self.lib.khp_debug_hair_sample(
+            self.ptr, n, int(lobes), ip(ob), ip(mt), N.fptr(ri), N.fptr(nn), N.fptr(hu), N.fptr(lu), ip(fl),
+            N.fptr(r["out"]), N.fptr(r["pdf"]), N.fptr(r["f"]), N.fptr(r["sample"]), ip(r["flags"]), ip(r["valid"])),
+            "khp_debug_hair_sample")
         return r
 
     def debug_bsdf_eval(self, obj, mat, ray_in, normal, out):

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define KHP_ABI_VERSION 15
+#define KHP_ABI_VERSION 16
 
 typedef struct khp_ctx khp_ctx;
 
@@ -411,6 +411,32 @@ void khp_bdpt_params_defaults(khp_bdpt_params* out);   /* off; 256 paths, 4 vert
 khp_status khp_set_bdpt(khp_ctx* ctx, const khp_bdpt_params* params);
 khp_status khp_get_bdpt(khp_ctx* ctx, khp_bdpt_params* out);
 
+/* ---- ABI 16: Marschner's TT and TRT fibre paths ------------------------------
+ * MarschnerHairBSDF::localSample (Bsdf.cpp:465-769) holds three lobes: R (surface
+ * reflection), TT (through the fibre) and TRT (one reflection inside it), the
+ * last two as a state machine carried across bounces in Bounce::mat_flags.  KIRK
+ * ships with the choice pinned to R (`int p = 0;`, :669), and so does a context
+ * by default: with lobes == KHP_HAIR_LOBE_R every frame, texture and query is
+ * what it was before ABI 16.  With other lobes enabled an unflagged hit on a
+ * Marschner material draws one of the enabled lobes uniformly (draw 9 of the
+ * bounce), TT / TRT refract into the fibre and the following one or two hits --
+ * each a bounce of `depth`, as in traceRays -- finish the path.
+ * d'Eon's TT / TRT stay unported.  Frames with TT or TRT have no CPU oracle.
+ * khp_set_hair_lobes completes in-flight frames and needs no rebuild; lobes == 0,
+ * bits above 7 or reserved != 0 are KHP_EINVAL.  The light-path variant traces
+ * the R lobe only: enabling it with TT or TRT on, or the reverse, is
+ * KHP_EUNSUPPORTED. */
+#define KHP_HAIR_LOBE_R   1u
+#define KHP_HAIR_LOBE_TT  2u
+#define KHP_HAIR_LOBE_TRT 4u
+typedef struct {
+    uint32_t lobes;      /* KHP_HAIR_LOBE_* bits, at least one */
+    uint32_t reserved;   /* 0 */
+} khp_hair_lobes;
+void khp_hair_lobes_defaults(khp_hair_lobes* out);   /* lobes = KHP_HAIR_LOBE_R */
+khp_status khp_set_hair_lobes(khp_ctx* ctx, const khp_hair_lobes* lobes);
+khp_status khp_get_hair_lobes(khp_ctx* ctx, khp_hair_lobes* out);
+
 /* Completes every frame enqueued with KHP_RENDER_ASYNC (ABI 5).  A progressive
  * caller (KIRK's PathTracer::render loop) enqueues its passes and syncs before
  * reading the texture; passes accumulate in call order.  Any synchronous call
@@ -624,6 +650,18 @@ khp_status khp_debug_bsdf_sample(khp_ctx* ctx, uint32_t n, uint32_t kinds_mask, 
                                  const int32_t* material, const float* in, const float* normal,
                                  const float* sample, const float* hair, const int32_t* flags_in, float* out_dir,
                                  float* pdf, float* f, float* sample_out, int32_t* flags_out, int32_t* valid);
+/* ABI 16: MarschnerHairBSDF::localSample with the lobe set `lobes` (the argument,
+ * not the context's setting) -- the device function the renderer calls when TT
+ * or TRT is on -- for the same kind of item: lobe_u[i] is the lobe draw of an
+ * unflagged first hit, hair[i][2] the alpha / beta draws, flags_in[i] the path's
+ * flags (MATFLAG_CYLINDER_T_BOUNCE 8, _TR_BOUNCE 16 select the call of the state
+ * machine).  Every material[i] must be KHP_BSDF_MARSCHNER_HAIR and `lobes` a
+ * non-empty subset of 7, else KHP_EINVAL.  Outputs as khp_debug_bsdf_sample's;
+ * the calls that only redirect the ray leave pdf and the sample at 0. */
+khp_status khp_debug_hair_sample(khp_ctx* ctx, uint32_t n, uint32_t lobes, const int32_t* object,
+                                 const int32_t* material, const float* in, const float* normal, const float* hair,
+                                 const float* lobe_u, const int32_t* flags_in, float* out_dir, float* pdf, float* f,
+                                 float* sample_out, int32_t* flags_out, int32_t* valid);
 /* BSDF::evaluateLight for the same kind of item and the direction out[i]: f [n][3]. */
 khp_status khp_debug_bsdf_eval(khp_ctx* ctx, uint32_t n, const int32_t* object, const int32_t* material,
                                const float* in, const float* normal, const float* out, float* f);

@@ -181,6 +181,16 @@ class Context {
         return p;
     }
     void set_bdpt(const khp_bdpt_params& p) { check(khp_set_bdpt(c_, &p), "khp_set_bdpt"); }
+    // ABI 16: the lobes of Marschner's fibre model (KHP_HAIR_LOBE_* bits; R alone is KIRK as shipped)
+    uint32_t hair_lobes() {
+        khp_hair_lobes p{};
+        check(khp_get_hair_lobes(c_, &p), "khp_get_hair_lobes");
+        return p.lobes;
+    }
+    void set_hair_lobes(uint32_t lobes) {
+        const khp_hair_lobes p{lobes, 0u};
+        check(khp_set_hair_lobes(c_, &p), "khp_set_hair_lobes");
+    }
     void render(const khp_render_params& p, float* out_rgb = nullptr) {
         check(khp_render(c_, &p, out_rgb), "khp_render");
     }

@@ -1,0 +1,204 @@
+"""Marschner's TT and TRT fibre paths (ABI 16), the parts that need no device: the
+switch's defaults and refusals, and the float64 reference of the three-call state
+machine (tests/_hairref.py) against known answers worked out by hand.
+"""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+
+import _hairref as H
+import _shaderef as R
+import ba_pathtracing_fur_amd as P
+from ba_pathtracing_fur_amd import native as N
+
+TOP = 1.0 - 2.0 ** -24
+T, TR, SPEC = R.F_CYL_T, R.F_CYL_TR, R.F_SPECULAR
+
+
+def test_defaults_and_layout():
+    lib = N.load_library()
+    hl = N.HairLobes(99, 99)
+    lib.khp_hair_lobes_defaults(ctypes.byref(hl))
+    assert (hl.lobes, hl.reserved) == (1, 0)
+    lib.khp_hair_lobes_defaults(None)                 # a null pointer is ignored, as the other defaults functions do
+    assert ctypes.sizeof(N.HairLobes) == 8
+    assert (P.HAIR_LOBE_R, P.HAIR_LOBE_TT, P.HAIR_LOBE_TRT) == (1, 2, 4)
+    assert {"HAIR_LOBE_R", "HAIR_LOBE_TT", "HAIR_LOBE_TRT"} <= set(P.__all__)
+    assert N.ABI_VERSION == 16 == lib.khp_abi_version()
+
+
+def test_null_arguments_are_refused_without_a_device():
+    lib = N.load_library()
+    hl = N.HairLobes(1, 0)
+    for call in (lambda: lib.khp_set_hair_lobes(None, ctypes.byref(hl)), lambda: lib.khp_get_hair_lobes(None, ctypes.byref(hl)),
+                 lambda: lib.khp_set_hair_lobes(None, None)):
+        assert call() == N.KHP_EINVAL
+        assert b"null" in lib.khp_last_error()
+    f = lambda *s: np.zeros(s, np.float32).ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    i = lambda: np.zeros(4, np.int32).ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    assert lib.khp_debug_hair_sample(None, 4, 7, i(), i(), f(4, 3), f(4, 3), f(4, 2), f(4), i(), f(4, 3), f(4), f(4, 3),
+                                     f(4, 2), i(), i()) == N.KHP_EINVAL
+    assert b"null" in lib.khp_last_error()
+
+
+# ---- the reference ---------------------------------------------------------------------------------
+def _items(n, seed):
+    rng = np.random.default_rng(seed)
+    unit32 = lambda v: (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(np.float32)
+    wi, nn = unit32(rng.normal(size=(n, 3))), unit32(rng.normal(size=(n, 3)))
+    v = unit32(rng.normal(size=(n, 3))).astype(np.float64)
+    u = R.unit(R.cross(v, np.array([0.0, 1.0, 0.0])))
+    frame = np.stack([u, v, R.unit(R.cross(u, v))], axis=1)
+    mat = {"diffuse": rng.uniform(0.1, 0.9, (n, 3)), "ior": rng.uniform(1.2, 1.8, n)}
+    return mat, frame, wi, nn, rng.random((n, 2), np.float32), rng.random(n, np.float32)
+
+
+def test_r_branch_is_shaderefs_marschner_sample():
+    n = 4096
+    mat, frame, wi, nn, hair, lu = _items(n, 7)
+    full = dict(mat, specular=np.zeros((n, 3)), volume=np.zeros((n, 3)), roughness=np.zeros(n))
+    want = R.bsdf_sample(R.MARSCHNER, full, frame, wi, nn, np.zeros((n, 2)), hair, np.zeros(n, np.int32))
+    for lobes, u in ((H.LOBE_R, lu), (7, lu * np.float32(1 / 3) * np.float32(TOP)), (H.LOBE_R | H.LOBE_TRT, lu * np.float32(0.49))):
+        got = H.hair_sample(mat, frame, wi, nn, hair, u, np.zeros(n, np.int32), lobes)
+        for k in ("out", "pdf", "f", "sample", "flags", "valid"):
+            np.testing.assert_array_equal(got[k], want[k], err_msg=f"lobes {lobes}: {k}")
+
+
+def test_flag_transitions():
+    n = 64
+    mat, frame, wi, nn, hair, lu = _items(n, 8)
+    zero = np.zeros(n, np.int32)
+    run = lambda lobes, flags: H.hair_sample(mat, frame, wi, nn, hair, lu, flags, lobes)
+    a = run(H.LOBE_TT, zero)                                   # unflagged, p = 1
+    assert np.all(a["flags"] == T) and not a["f"].any() and not a["pdf"].any()
+    b = run(H.LOBE_TT, a["flags"])                             # CYL_T: the TT exit
+    assert np.all(b["flags"] == 0) and np.all(b["pdf"] > 0)
+    a = run(H.LOBE_TRT, zero)                                  # unflagged, p = 2
+    assert np.all(a["flags"] == TR) and not a["f"].any()
+    b = run(H.LOBE_TRT, a["flags"])                            # CYL_TR: the far wall
+    assert np.all(b["flags"] == (TR | T | SPEC)) and not b["f"].any() and not b["pdf"].any()
+    np.testing.assert_allclose(b["out"], R.reflect(-wi.astype(np.float64), nn.astype(np.float64)), atol=1e-12)
+    c = run(H.LOBE_TRT, b["flags"])                            # both: the TRT exit
+    assert np.all(c["flags"] == 0) and np.all(c["pdf"] > 0)
+    # the state, not the lobe set, selects the later calls
+    for k in ("out", "pdf", "f", "flags"):
+        np.testing.assert_array_equal(run(H.LOBE_R, b["flags"])[k], c[k])
+    assert list(H.call_of([0, SPEC, T, T | SPEC, TR, TR | SPEC, TR | T, TR | T | SPEC])) == [0, 0, 1, 1, 2, 2, 3, 3]
+
+
+def _one(flags, lobes, ior=1.55, lobe_u=0.0):
+    """in = n = +x on a fibre along +z (U = V x y = -x, W = U x V = +y), both hair draws 0: alpha = -5, beta = 5."""
+    x = np.array([[1.0, 0.0, 0.0]])
+    frame = np.array([[[-1.0, 0.0, 0.0], [0.0, 0.0, 1.0], [0.0, 1.0, 0.0]]])
+    mat = {"diffuse": np.array([[0.4, 0.3, 0.2]]), "ior": np.array([ior])}
+    r = H.hair_sample(mat, frame, x, x, np.zeros((1, 2)), np.array([lobe_u]), np.array([flags]), lobes)
+    return {k: v[0] for k, v in r.items()}
+
+
+def _gauss(x, sd):
+    return math.exp(-0.5 * (x / sd) ** 2) / (sd * math.sqrt(2 * math.pi))
+
+
+def test_analytic_item_per_lobe():
+    """Normal incidence: gamma_i = 0, h = 0.  KIRK hands the *angle* 0 to dialectricFresnel as a cosine, so F = 1
+    (the media swap at cos <= 0 and sin_t = eta/eta * 1 reaches 1): R reflects everything, and (1 - F)^2 makes
+    both transmitted lobes black.  The directions, theta_i, and the longitudinal Gaussians are worked out below."""
+    pi = math.pi
+    # R: the mirror direction +x turned about +z by -alpha = 5 rad; theta is measured from U = -x in the (V, U, W) frame,
+    # so theta_i = pi and theta_r = 5 - pi; theta_h = 2.5, x = theta_h - alpha = 7.5, theta_d = 2.5 - pi
+    r = _one(0, H.LOBE_R)
+    np.testing.assert_allclose(r["out"], [math.cos(5), math.sin(5), 0], atol=1e-15)
+    pdf = _gauss(7.5, 5.0)
+    np.testing.assert_allclose(r["pdf"], pdf, rtol=1e-14)
+    np.testing.assert_allclose(r["f"], [pdf * (0.5 * 1 * 2) / math.cos(2.5) ** 2] * 3, rtol=1e-12)   # dh/dphi = 2
+    np.testing.assert_allclose(r["sample"], [pi, 0], rtol=1e-15)
+    assert r["flags"] == SPEC
+    # the first hit of TT / TRT: Snell at normal incidence goes straight on
+    for lobes, fl in ((H.LOBE_TT, T), (H.LOBE_TRT, TR)):
+        r = _one(0, lobes)
+        np.testing.assert_allclose(r["out"], [-1, 0, 0], atol=1e-15)
+        assert r["flags"] == fl and not r["f"].any() and r["pdf"] == 0 and not r["sample"].any()
+    # TT exit: unbent -x, turned by alpha / 2 = -2.5: (-cos 2.5, sin 2.5, 0); theta_r = 2.5,
+    # x = (2.5 + pi) / 2 + alpha / 2 = (pi - 2.5) / 2, sd = beta / 2
+    r = _one(T, H.LOBE_R)
+    np.testing.assert_allclose(r["out"], [-math.cos(2.5), math.sin(2.5), 0], atol=1e-15)
+    np.testing.assert_allclose(r["pdf"], _gauss((pi - 2.5) / 2, 2.5), rtol=1e-13)
+    np.testing.assert_allclose(r["sample"], [pi, 0], rtol=1e-15)
+    assert r["flags"] == 0 and not r["f"].any() and np.all(np.isfinite(r["f"]))
+    # the far wall: -x again mirrors back to +x
+    r = _one(TR, H.LOBE_R)
+    np.testing.assert_allclose(r["out"], [1, 0, 0], atol=1e-15)
+    assert r["flags"] == (TR | T | SPEC) and not r["f"].any()
+    # TRT exit: turned by 3 alpha / 2 = -7.5: (-cos 7.5, sin 7.5, 0); theta_r = 7.5 - 2 pi,
+    # x = (7.5 - 2 pi + pi) / 2 - 7.5 = -(7.5 + pi) / 2, sd = 2 beta
+    r = _one(TR | T | SPEC, H.LOBE_R)
+    np.testing.assert_allclose(r["out"], [-math.cos(7.5), math.sin(7.5), 0], atol=1e-15)
+    np.testing.assert_allclose(r["pdf"], _gauss((7.5 + pi) / 2, 10.0), rtol=1e-13)
+    assert r["flags"] == 0 and not r["f"].any() and np.all(np.isfinite(r["f"]))
+
+
+def test_analytic_exit_weights_off_axis():
+    """A second hand-worked item where the transmitted lobes are not black: in at 60 degrees to n in the fibre's
+    normal plane, ior 1.5.  gamma = pi/3, h = sin gamma; eta' = sqrt(ior^2 - h^2) / cos gamma."""
+    g, ior = math.pi / 3, 1.5
+    n = np.array([[1.0, 0.0, 0.0]])
+    wi = np.array([[math.cos(g), math.sin(g), 0.0]])
+    frame = np.array([[[-1.0, 0.0, 0.0], [0.0, 0.0, 1.0], [0.0, 1.0, 0.0]]])
+    sigma = np.array([0.4, 0.3, 0.2])
+    mat = {"diffuse": sigma[None], "ior": np.array([ior])}
+    gamma = math.acos(math.cos(g))
+    h = math.sin(gamma)
+    x1 = math.sqrt(ior * ior - h * h)
+    e1, e2 = x1 / math.cos(gamma), ior * ior * math.cos(gamma) / x1
+    c = math.asin(1 / e1)
+
+    def fres(cos_t, ei, et):                                    # dialectricFresnel on a "cosine" in (0, 1]
+        si = math.sqrt(1 - cos_t * cos_t)
+        st = ei / et * si
+        if st >= 1:
+            return 1.0
+        ct = math.sqrt(1 - st * st)
+        rp = (et * cos_t - ei * ct) / (et * cos_t + ei * ct)
+        rs = (ei * cos_t - et * ct) / (ei * cos_t + et * ct)
+        return (rp * rp + rs * rs) / 2
+    F = fres(min(gamma, 1.0), e1, e2)                           # the angle, clamped as a cosine
+    # both exits leave along -wi, which lies in the U-W plane and is turned about V within it: theta_i is the angle
+    # of wi from U = -x, theta_r that of the turned -wi
+    for flags, turn, sd, scale in ((T, -2.5, 2.5, 1.0), (TR | T, -7.5, 10.0, 10.0)):
+        r = H.hair_sample(mat, frame, wi, n, np.zeros((1, 2)), np.zeros(1), np.array([flags]), H.LOBE_R)
+        a = g + math.pi + turn                                  # the polar angle of the exit direction in the x-y plane
+        out = np.array([math.cos(a), math.sin(a), 0.0])
+        np.testing.assert_allclose(r["out"][0], out, atol=1e-14)
+        ti = math.atan2(abs(wi[0, 1]), -wi[0, 0])
+        tr = math.atan2(abs(out[1]), -out[0])
+        pdf = _gauss((tr + ti) / 2 + turn, sd)
+        sig = sigma / math.cos(tr)
+        if flags == T:
+            dh = 1 / abs((1 / math.sqrt(1 - h * h)) * (-(24 * c / math.pi ** 3) * gamma ** 2 + (6 * c / math.pi - 2)))
+            att = (1 - F) ** 2 * np.exp(sig * (-2 * math.cos(math.asin(h / e1))))
+        else:
+            dh = 1 / abs((1 / math.sqrt(1 - h * h)) * (-(48 * c / math.pi ** 3) * gamma ** 2 + (12 * c / math.pi - 2)))
+            gt = math.asin(h / e1)
+            att = (1 - F) ** 2 * fres(min(gt, 1.0), 1 / e1, 1 / e2) * np.exp(sig * (-2 * math.cos(gt))) ** 2
+        want = scale * pdf * (0.5 * att * dh) / math.cos((tr - ti) / 2) ** 2
+        np.testing.assert_allclose(r["pdf"][0], pdf, rtol=1e-12)
+        np.testing.assert_allclose(r["f"][0], want, rtol=1e-11)
+        assert np.all(want > 0) and r["flags"][0] == 0
+
+
+@pytest.mark.parametrize("lobes", range(1, 8))
+def test_lobe_choice(lobes):
+    enabled = [p for p in range(3) if (lobes >> p) & 1]
+    for dt in (np.float64, np.float32):
+        u = np.array([0.0, 1 / 3, 2 / 3, TOP], dt)
+        k = [min(len(enabled) - 1, int(float(x) * len(enabled))) for x in u.astype(np.float64)]
+        assert list(H.lobe_pick(lobes, u)) == [enabled[i] for i in k]
+    # spelled out: the all-three set is KIRK's uniform_int_distribution(0, 2)
+    want = {1: [0, 0, 0, 0], 2: [1, 1, 1, 1], 4: [2, 2, 2, 2], 3: [0, 0, 1, 1], 5: [0, 0, 2, 2], 6: [1, 1, 2, 2],
+            7: [0, 1, 2, 2]}[lobes]
+    assert list(H.lobe_pick(lobes, np.array([0.0, 1 / 3, 2 / 3, TOP]))) == want
+    # and the state machine follows the choice
+    for u, p in zip((0.0, 1 / 3, 2 / 3, TOP), want):
+        assert _one(0, lobes, lobe_u=u)["flags"] == (SPEC, T, TR)[p]
