@@ -20,9 +20,10 @@ def set_hw_queues(n: int = 8) -> None:
 
 
 from . import native  # noqa: E402,F401
-from .native import HAIR_LOBE_R, HAIR_LOBE_TRT, HAIR_LOBE_TT  # noqa: E402
+from .native import AOV_CHANNELS, HAIR_LOBE_R, HAIR_LOBE_TRT, HAIR_LOBE_TT, AovBuffers  # noqa: E402
 from .pathtracer import BVH, BsdfFactory, HipContext, PathTracer, ShaderFactory, comm_unique_id  # noqa: E402
 from .scenes import SceneData, build_config  # noqa: E402
 
 __all__ = ["set_hw_queues", "native", "BVH", "BsdfFactory", "HipContext", "PathTracer", "ShaderFactory", "SceneData",
-           "build_config", "comm_unique_id", "HAIR_LOBE_R", "HAIR_LOBE_TT", "HAIR_LOBE_TRT"]
+           "build_config", "comm_unique_id", "HAIR_LOBE_R", "HAIR_LOBE_TT", "HAIR_LOBE_TRT", "AovBuffers",
+           "AOV_CHANNELS"]

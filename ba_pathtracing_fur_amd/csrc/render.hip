@@ -2792,6 +2792,7 @@ struct khp_ctx {
         khp_render_params next{};
         uint64_t gen = 0;
     } series;
+    std::shared_ptr<struct AovState> aov;   // khp_render_aov's own scratch (aov.h), made by its first call
 };
 constexpr size_t LG_SLOTS = 64;
 
@@ -5023,6 +5024,7 @@ extern "C" khp_status khp_debug_queue(khp_ctx* c, uint32_t* n, float* orig, floa
 }
 
 #include "debug_query.h"   // ABI 15: khp_debug_surface / _bsdf_sample / _bsdf_eval / _light_dir / _light_isect
+#include "aov.h"           // khp_render_aov: per-pixel first-hit feature buffers
 
 extern "C" khp_status khp_read_framebuffer(khp_ctx* c, float* out_rgb) {
     if (c) {  // complete asynchronous frames first

@@ -149,6 +149,17 @@ class HairLobes(ctypes.Structure):
     _fields_ = [("lobes", c_uint32), ("reserved", c_uint32)]
 
 
+class AovBuffers(ctypes.Structure):
+    """khp_aov_buffers (48 bytes): the planes khp_render_aov writes; a null plane is not computed."""
+    _fields_ = [("normal", POINTER(c_float)), ("albedo", POINTER(c_float)), ("tangent", POINTER(c_float)),
+                ("depth", POINTER(c_float)), ("coverage", POINTER(c_float)), ("object", POINTER(c_int32))]
+
+
+# khp_aov_buffers' planes in struct order: name -> (trailing shape, dtype)
+AOV_CHANNELS = {"normal": ((3,), np.float32), "albedo": ((3,), np.float32), "tangent": ((3,), np.float32),
+                "depth": ((), np.float32), "coverage": ((), np.float32), "object": ((), np.int32)}
+
+
 class Tonemap(ctypes.Structure):
     """khp_tonemap: KIRK::Tonemapper's parameters (Utils/Tonemapping.h:22-33)."""
     _fields_ = [("exposure", c_float), ("bias", c_float), ("gamma", c_float), ("contrast", c_float),
@@ -204,7 +215,7 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_tonemap_log_sum", "khp_set_camera", "khp_debug_comm_wait", "khp_fur_params_defaults",
             "khp_fur_count", "khp_gen_fur", "khp_gen_fur_device", "khp_debug_surface", "khp_debug_bsdf_sample",
             "khp_debug_bsdf_eval", "khp_debug_light_dir", "khp_debug_light_isect", "khp_hair_lobes_defaults",
-            "khp_set_hair_lobes", "khp_get_hair_lobes", "khp_debug_hair_sample"]
+            "khp_set_hair_lobes", "khp_get_hair_lobes", "khp_debug_hair_sample", "khp_render_aov"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
 ABI_VERSION = 16
@@ -242,6 +253,7 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_set_scene": (c_int, [c_void_p, P(SceneDesc)]),
         "khp_build_accel": (c_int, [c_void_p]),
         "khp_render": (c_int, [c_void_p, P(RenderParams), c_void_p]),
+        "khp_render_aov": (c_int, [c_void_p, P(RenderParams), P(AovBuffers)]),
         "khp_sync": (c_int, [c_void_p]),
         "khp_ctx_params_defaults": (None, [P(CtxParams)]),
         "khp_set_params": (c_int, [c_void_p, P(CtxParams)]),
@@ -323,7 +335,10 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
     if abi != ABI_VERSION:   # the structs above would be read with the wrong layout
         raise RuntimeError(f"{p}: ABI {abi}, this package needs ABI {ABI_VERSION} (rebuild: __graft_entry__.build())")
     for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:   # a library of this ABI built before the symbol was added
+            raise RuntimeError(f"{p}: no symbol {name}, this package needs it (rebuild: __graft_entry__.build())") from None
         fn.restype = res
         fn.argtypes = args
     if path is None:

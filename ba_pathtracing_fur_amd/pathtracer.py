@@ -248,6 +248,34 @@ class HipContext:
         N.check(self.lib, self.lib.khp_render(self.ptr, ctypes.byref(p), ptr), "khp_render")
         return out
 
+    AOV_CHANNELS = tuple(N.AOV_CHANNELS)   # normal, albedo, tangent, depth, coverage, object
+
+    def render_aov(self, width, height, spp, seed=0x4B49524B, first_sample=0, tile_size=64, tile_rank=0,
+                   tile_nranks=1, channels=AOV_CHANNELS, out: dict | None = None) -> dict:
+        """khp_render_aov: the first hit's features per pixel over samples first_sample ..
+        first_sample + spp - 1 of the rays render() traces -- normal, albedo, tangent (H, W, 3),
+        depth, coverage (H, W) float32, each the sample mean premultiplied by coverage, and
+        object (H, W) int32, the first sample's object id or -1 -- as a dict of the `channels`
+        asked for.  Renders nothing: framebuffer, sample counts and frames in flight stay as
+        they are.  `out` supplies the arrays to write into (a tile rank leaves the pixels it
+        does not own untouched); otherwise they start as zeros."""
+        channels = tuple(channels)
+        for ch in channels:
+            if ch not in N.AOV_CHANNELS:
+                raise ValueError(f"khp_render_aov has no channel {ch!r} (one of {', '.join(N.AOV_CHANNELS)})")
+        res, buf = {}, N.AovBuffers()
+        for ch in channels:
+            tail, dtype = N.AOV_CHANNELS[ch]
+            a = out[ch] if out is not None and ch in out else np.zeros((height, width) + tail, dtype)
+            if a.dtype != dtype or a.shape != (height, width) + tail or not a.flags.c_contiguous:
+                raise ValueError(f"channel {ch}: a C-contiguous {np.dtype(dtype).name} array of shape "
+                                 f"{(height, width) + tail} is needed")
+            setattr(buf, ch, a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32 if ch == "object" else ctypes.c_float)))
+            res[ch] = a
+        p = N.RenderParams(width, height, spp, 0, seed, first_sample, tile_size, tile_rank, tile_nranks, 0)
+        N.check(self.lib, self.lib.khp_render_aov(self.ptr, ctypes.byref(p), ctypes.byref(buf)), "khp_render_aov")
+        return res
+
     def sync(self):
         """khp_sync: complete every asynchronous frame; stats() then sums them."""
         N.check(self.lib, self.lib.khp_sync(self.ptr), "khp_sync")

@@ -381,6 +381,49 @@ khp_status khp_build_accel(khp_ctx* ctx);
  * Pixels of tiles not owned by this rank are left untouched. */
 khp_status khp_render(khp_ctx* ctx, const khp_render_params* p, float* out_rgb);
 
+/* ---- per-pixel first-hit feature buffers (AOVs) ------------------------------
+ * What a denoiser or compositor wants beside the colour: for every pixel this
+ * rank owns and the samples k = first_sample .. first_sample + spp - 1, the
+ * camera rays khp_render traces for those samples (the context's current camera)
+ * and the surface at their first hit.  A sample is a surface sample when its
+ * closest object hit exists (the hit khp_trace_closest reports) and no light's
+ * own intersection is nearer (t_light < t_hit ends the path on the light, as in
+ * traceRay).  A surface sample contributes
+ *   normal   the shading normal (khp_debug_surface's; not face-forwarded),
+ *   tangent  the hit object's hair frame V (KHP_AOV_TANGENT_IS_FRAME_V),
+ *   albedo   the resolved material's diffuse (textured scenes: the texel's),
+ *   depth    the hit's t along the normalised ray,
+ *   coverage 1;
+ * any other sample contributes +0 to every channel.  Each float channel is
+ * s / (float)spp, where s starts at +0 and takes the samples' values in
+ * increasing k with float32 adds: normal, tangent, albedo and depth are
+ * premultiplied by coverage, a host divides.  object is the object id of sample
+ * first_sample (-1 when that is not a surface sample).  The result is a function
+ * of the arguments alone (no atomics, no scheduling-dependent order).
+ *
+ * p as for khp_render: width, height, spp, seed, first_sample and tile_* are
+ * used, depth is ignored, flags is 0 or KHP_RENDER_OUT_DEVICE (then every
+ * pointer is device memory of ctx's GPU).  A NULL buffer is not computed; pixels
+ * of tiles this rank does not own are left untouched (hosts assemble tiles by
+ * khp_gather_plan).  KHP_EINVAL: another flag, every buffer NULL, spp == 0 or
+ * above 2^24, width * height == 0, a null argument; KHP_ENOTREADY without a
+ * scene or a tree.  The arguments are checked before the context is touched.
+ *
+ * The call renders nothing: framebuffer, sample counters, khp_stats, render-ahead
+ * work and asynchronous frames (pending or in flight) are left as they are; it is
+ * only queued behind what the context's stream holds, and returns when its
+ * buffers are written.  KIRK has no counterpart. */
+#define KHP_AOV_TANGENT_IS_FRAME_V 1   /* documentation only: tangent = the hit object's V axis */
+typedef struct {
+    float*   normal;    /* [H][W][3] or NULL */
+    float*   albedo;    /* [H][W][3] or NULL */
+    float*   tangent;   /* [H][W][3] or NULL */
+    float*   depth;     /* [H][W]    or NULL */
+    float*   coverage;  /* [H][W]    or NULL */
+    int32_t* object;    /* [H][W]    or NULL */
+} khp_aov_buffers;
+khp_status khp_render_aov(khp_ctx* ctx, const khp_render_params* p, const khp_aov_buffers* out);
+
 /* ABI 7: the light-path (bidirectional) variant of KIRK's GLSL path tracer,
  * lbb_construction.compute:195-403 builds light subpaths
  * (generatePrimaryLightRays / traceLightRays / shadeLightRays) and

@@ -194,6 +194,11 @@ class Context {
     void render(const khp_render_params& p, float* out_rgb = nullptr) {
         check(khp_render(c_, &p, out_rgb), "khp_render");
     }
+    // The first hit's features per pixel for the samples p names (khp_render_aov): the buffers of
+    // `out` that are not null; p.flags 0 (host buffers) or KHP_RENDER_OUT_DEVICE.  Renders nothing.
+    void render_aov(const khp_render_params& p, const khp_aov_buffers& out) {
+        check(khp_render_aov(c_, &p, &out), "khp_render_aov");
+    }
     // KHP_RENDER_ASYNC renders are complete (and accumulated in call order) after sync()
     void sync() { check(khp_sync(c_), "khp_sync"); }
     void read_framebuffer(float* out_rgb) { check(khp_read_framebuffer(c_, out_rgb), "khp_read_framebuffer"); }
