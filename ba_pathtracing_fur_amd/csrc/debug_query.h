@@ -4,8 +4,10 @@
 // renderer calls -- trace_closest, surface_at, bsdf_sample<KINDS>, bsdf_eval,
 // light_dir, light_isect, light_emit, and (ABI 16) bsdf_sample's KINDS_LOBES
 // instance, hair_lobes.h -- so a test can compare them item by item
-// with the oracle and with a float64 reference.  Every index is checked on the
-// host before a launch; the kernels read nothing the host has not validated.
+// with the oracle and with a float64 reference.  ABI 17 adds the light-path
+// variant's: k_light_paths itself, bd_connection and img_connection (at the end).
+// Every index is checked on the host before a launch; the kernels read nothing
+// the host has not validated.
 #pragma once
 
 constexpr uint32_t DBG_MAX_ITEMS = 1u << 20;
@@ -399,5 +401,221 @@ extern "C" khp_status khp_debug_light_isect(khp_ctx* c, uint32_t n, const int32_
     HIPCHK(hipMemcpyAsync(t_out, dt.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(emit, de.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     KHPCHK(wait_stream(c, c->stream, "the light queries"));
+    return KHP_OK;
+}
+
+// ---- ABI 17: queries of the light-path variant (lightpath.h) --------------
+// khp_debug_light_paths launches k_light_paths itself on scratch of its own;
+// k_dbg_lv_unpack turns its 48-B vertices into the oracle's 10-float records (the
+// kernel leaves din / hc of an invalid vertex unwritten: they come back as zeros).
+constexpr uint32_t DBG_MAX_VERT = 16;   // khp_bdpt_params.vertices' upper bound
+
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_lv_unpack(uint32_t n, const float4* lv, float* out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float4 a = lv[3 * (size_t)i];
+        float* o = out + 10 * (size_t)i;
+        const bool ok = a.w != 0.0f;
+        const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const float4 d = ok ? lv[3 * (size_t)i + 1] : z, h = ok ? lv[3 * (size_t)i + 2] : z;
+        o[0] = ok ? 1.0f : 0.0f;
+        st3(o + 1, ok ? mk(a.x, a.y, a.z) : mk(0.0f, 0.0f, 0.0f));
+        st3(o + 4, mk(d.x, d.y, d.z));
+        st3(o + 7, mk(h.x, h.y, h.z));
+    }
+}
+
+// One hit connection per item: trace_closest and surface_at as k_dbg_surface, then
+// bd_connection.  recs holds item i's vertex at record DBG_MAX_VERT + i, so that
+// bd_connection's v[3 * j] (j < DBG_MAX_VERT) is that record and v stays inside recs.
+template <bool TEX>
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_bdpt_connect(DevScene S, BdptDev bd, uint32_t n, const float* orig,
+                                                                const float* dir, const uint32_t* bounce,
+                                                                const int32_t* li, const uint32_t* vj,
+                                                                const float4* recs, uint8_t* hit, uint8_t* acc,
+                                                                float* ro, float* rd, float* tmax, float* cj) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const Ray r = make_ray(ld3(orig + 3 * (size_t)i), ld3(dir + 3 * (size_t)i));
+        Hit h;
+        PrivStack stk;
+        TravStats st{0, 0};
+        trace_closest<false>(S, r, h, stk, st);
+        const v3 zero = mk(0.0f, 0.0f, 0.0f);
+        Ray sh;
+        sh.o = sh.d = zero;
+        float tm = 0.0f;
+        v3 col = zero;
+        bool ok = false;
+        if (h.slot >= 0) {
+            ShadeCtx s;
+            khp_material mres;
+            surface_at<TEX>(S, r, h, s, mres);
+            const uint32_t j = vj[i];
+            ok = bd_connection(S, bd, recs + 3 * ((size_t)i + DBG_MAX_VERT - j), j, S.lights[li[i]], s, follow(r, h.t),
+                               r.d, bounce[i], sh, tm, col);
+            if (!ok) {
+                sh.o = sh.d = col = zero;
+                tm = 0.0f;
+            }
+        }
+        hit[i] = h.slot >= 0 ? 1 : 0;
+        acc[i] = ok ? 1 : 0;
+        st3(ro + 3 * (size_t)i, sh.o);
+        st3(rd + 3 * (size_t)i, sh.d);
+        tmax[i] = tm;
+        st3(cj + 3 * (size_t)i, col);
+    }
+}
+
+// One image-plane connection per item: img_sensor and img_connection as k_img_connect.
+// recs: DBG_MAX_VERT records of padding, then records j - 1 and j of item i at 2 i and
+// 2 i + 1, so that img_connection's lv[3 * (j - 1)] and lv[3 * j] are those and lv stays inside recs.
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_img_connect(DevScene S, BdptDev bd, uint32_t W, uint32_t H, uint32_t n,
+                                                               const float* sensor, const uint32_t* vj,
+                                                               const float4* recs, uint8_t* acc, float* dir_out,
+                                                               float* t_out, float* cj_out) {
+    float a;
+    v3 cn;
+    img_sensor(S.cam, W, H, a, cn);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t j = vj[i];
+        const float4* lv = recs + 3 * (2 * (size_t)i + 1 + DBG_MAX_VERT - j);
+        v3 dir = mk(0.0f, 0.0f, 0.0f), cj = dir;
+        float t = 0.0f;
+        const bool ok = img_connection(bd.img, bd.bias, bd.bounce_bias, lv, j, ld3(sensor + 3 * (size_t)i), a, cn, dir, t, cj);
+        if (!ok) {
+            dir = cj = mk(0.0f, 0.0f, 0.0f);
+            t = 0.0f;
+        }
+        acc[i] = ok ? 1 : 0;
+        st3(dir_out + 3 * (size_t)i, dir);
+        t_out[i] = t;
+        st3(cj_out + 3 * (size_t)i, cj);
+    }
+}
+
+static khp_status dbg_bdpt_params(khp_ctx* c) {
+    if (c->bd.light_paths < 1 || c->bd.light_paths > 65536) return fail(KHP_EINVAL, "light_paths must be 1..65536");
+    if (c->bd.vertices < 1 || c->bd.vertices > DBG_MAX_VERT) return fail(KHP_EINVAL, "vertices must be 1..16");
+    return KHP_OK;
+}
+
+static BdptDev dbg_bdpt_dev(khp_ctx* c, const float4* lv) {
+    return BdptDev{1u, c->bd.light_paths, (uint32_t)c->S.n_lights, c->bd.vertices, c->bd.bias, c->bd.bounce_bias,
+                   c->bd.min_pdf, c->bd.image_plane, lv};
+}
+
+// 10-float records -> the device's three float4 per vertex
+static void dbg_pack_vertex(const float* r, float4* o) {
+    o[0] = make_float4(r[1], r[2], r[3], r[0] != 0.0f ? 1.0f : 0.0f);
+    o[1] = make_float4(r[4], r[5], r[6], 0.0f);
+    o[2] = make_float4(r[7], r[8], r[9], 0.0f);
+}
+
+extern "C" khp_status khp_debug_light_paths(khp_ctx* c, uint32_t seed, uint32_t k, float* out) {
+    KHPCHK(dbg_enter(c, 1, out != nullptr));
+    KHPCHK(dbg_bdpt_params(c));
+    if (c->S.n_lights <= 0) return fail(KHP_EINVAL, "the scene has no lights");
+    const uint64_t nsub = (uint64_t)c->bd.light_paths * (uint64_t)c->S.n_lights;
+    const uint64_t nv = nsub * c->bd.vertices;
+    if (nv > DBG_MAX_ITEMS) return fail(KHP_EINVAL, "light_paths x lights x vertices must be at most 2^20");
+    DevMem lv, o;
+    HIPCHK(lv.ensure(48 * (size_t)nv));
+    HIPCHK(o.ensure(40 * (size_t)nv));
+    Wave Wv{};   // k_light_paths reads the seed, the sample slots and bd only
+    Wv.seed = seed;
+    Wv.n_frames = 1;
+    Wv.n_samples = 1;
+    Wv.sample0 = k;
+    Wv.fsample0[0] = k;
+    Wv.bd = dbg_bdpt_dev(c, lv.as<float4>());
+    hipLaunchKernelGGL(k_light_paths, dim3(((uint32_t)nsub + 63) / 64), dim3(64), 0, c->stream, c->S, Wv);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_dbg_lv_unpack, dim3(dbg_grid((uint32_t)nv)), dim3(DBG_BLOCK), 0, c->stream, (uint32_t)nv,
+                       lv.as<float4>(), o.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, o.p, 40 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the light-path query"));
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_debug_bdpt_connect(khp_ctx* c, uint32_t n, const float* orig, const float* dir,
+                                             const uint32_t* bounce, const int32_t* light, const uint32_t* j,
+                                             const float* vertex, uint8_t* hit, uint8_t* accepted, float* ray_orig,
+                                             float* ray_dir, float* tmax, float* cj) {
+    KHPCHK(dbg_enter(c, n, orig && dir && bounce && light && j && vertex && hit && accepted && ray_orig && ray_dir &&
+                               tmax && cj));
+    KHPCHK(dbg_light_items(c, n, light));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (j[i] >= DBG_MAX_VERT) return fail(KHP_EINVAL, "item " + std::to_string(i) + ": vertex index must be below 16");
+        if (bounce[i] > 4095u) return fail(KHP_EINVAL, "item " + std::to_string(i) + ": bounce must be at most 4095");
+    }
+    std::vector<float4> recs(3 * ((size_t)n + DBG_MAX_VERT), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    for (uint32_t i = 0; i < n; ++i) dbg_pack_vertex(vertex + 10 * (size_t)i, &recs[3 * ((size_t)i + DBG_MAX_VERT)]);
+    DevMem o, d, db, dl, dj, dr, oh, oa, oo, od, ot, oc;
+    HIPCHK(upload(o, orig, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(d, dir, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(db, bounce, (size_t)n, c->stream));
+    HIPCHK(upload(dl, light, (size_t)n, c->stream));
+    HIPCHK(upload(dj, j, (size_t)n, c->stream));
+    HIPCHK(upload(dr, recs.data(), recs.size(), c->stream));
+    HIPCHK(oh.ensure((size_t)n));
+    HIPCHK(oa.ensure((size_t)n));
+    HIPCHK(oo.ensure(12 * (size_t)n));
+    HIPCHK(od.ensure(12 * (size_t)n));
+    HIPCHK(ot.ensure(4 * (size_t)n));
+    HIPCHK(oc.ensure(12 * (size_t)n));
+    const BdptDev bd = dbg_bdpt_dev(c, nullptr);
+    if (c->S.textured)
+        hipLaunchKernelGGL(k_dbg_bdpt_connect<true>, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, bd, n,
+                           o.as<float>(), d.as<float>(), db.as<uint32_t>(), dl.as<int32_t>(), dj.as<uint32_t>(),
+                           dr.as<float4>(), oh.as<uint8_t>(), oa.as<uint8_t>(), oo.as<float>(), od.as<float>(),
+                           ot.as<float>(), oc.as<float>());
+    else
+        hipLaunchKernelGGL(k_dbg_bdpt_connect<false>, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, bd, n,
+                           o.as<float>(), d.as<float>(), db.as<uint32_t>(), dl.as<int32_t>(), dj.as<uint32_t>(),
+                           dr.as<float4>(), oh.as<uint8_t>(), oa.as<uint8_t>(), oo.as<float>(), od.as<float>(),
+                           ot.as<float>(), oc.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hit, oh.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(accepted, oa.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ray_orig, oo.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(ray_dir, od.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(tmax, ot.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(cj, oc.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the connection queries"));
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_debug_img_connect(khp_ctx* c, uint32_t width, uint32_t height, uint32_t n, const float* sensor,
+                                            const uint32_t* j, const float* prev, const float* cur, uint8_t* accepted,
+                                            float* dir, float* t, float* cj) {
+    KHPCHK(dbg_enter(c, n, sensor && j && prev && cur && accepted && dir && t && cj));
+    if (width == 0 || height == 0) return fail(KHP_EINVAL, "width and height must be positive");
+    if (c->bd.image_plane != 1u && c->bd.image_plane != 2u)
+        return fail(KHP_EINVAL, "khp_bdpt_params.image_plane must be 1 or 2");
+    for (uint32_t i = 0; i < n; ++i)
+        if (j[i] >= DBG_MAX_VERT) return fail(KHP_EINVAL, "item " + std::to_string(i) + ": vertex index must be below 16");
+    std::vector<float4> recs(3 * (2 * (size_t)n + DBG_MAX_VERT), make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    for (uint32_t i = 0; i < n; ++i) {
+        dbg_pack_vertex(prev + 10 * (size_t)i, &recs[3 * (2 * (size_t)i + DBG_MAX_VERT)]);
+        dbg_pack_vertex(cur + 10 * (size_t)i, &recs[3 * (2 * (size_t)i + 1 + DBG_MAX_VERT)]);
+    }
+    DevMem ds, dj, dr, oa, od, ot, oc;
+    HIPCHK(upload(ds, sensor, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(dj, j, (size_t)n, c->stream));
+    HIPCHK(upload(dr, recs.data(), recs.size(), c->stream));
+    HIPCHK(oa.ensure((size_t)n));
+    HIPCHK(od.ensure(12 * (size_t)n));
+    HIPCHK(ot.ensure(4 * (size_t)n));
+    HIPCHK(oc.ensure(12 * (size_t)n));
+    hipLaunchKernelGGL(k_dbg_img_connect, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S,
+                       dbg_bdpt_dev(c, nullptr), width, height, n, ds.as<float>(), dj.as<uint32_t>(), dr.as<float4>(),
+                       oa.as<uint8_t>(), od.as<float>(), ot.as<float>(), oc.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(accepted, oa.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(dir, od.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(t, ot.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(cj, oc.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the image-plane queries"));
     return KHP_OK;
 }

@@ -708,6 +708,46 @@ __global__ __launch_bounds__(64) void k_light_paths(DevScene S, Wave Wv) {
     }
 }
 
+// The sensor of a W x H frame as shadeBDPTImagePlane sees it: its area and the camera normal.
+__device__ __forceinline__ void img_sensor(const khp_camera& cam, uint32_t W, uint32_t H, float& a, v3& cn) {
+    const v3 axs = ld3(cam.axis_x) * cam.pixel_size, ays = ld3(cam.axis_y) * cam.pixel_size;
+    a = length(cross(ays * (float)H, axs * (float)W));
+    cn = normalize(cross(ays, axs));
+}
+
+// One image-plane connection (pt_shade.compute:38-92; the oracle's img_connection):
+// the visibility ray's direction and length from the sensor point to the target of
+// record j of the subpath lv, and the importance-weighted term; img, bias and
+// bounce_bias are BdptDev's.  Returns false for an invalid vertex.
+__device__ __forceinline__ bool img_connection(uint32_t img, float bias, float bounce_bias, const float4* lv, uint32_t j,
+                                               v3 sensor, float a, v3 cn, v3& dir, float& t, v3& cj) {
+    const float4 pv = lv[3 * j];
+    if (pv.w == 0.0f) return false;
+    const float4 din = lv[3 * j + 1], hc = lv[3 * j + 2];
+    const v3 dj = mk(din.x, din.y, din.z);
+    v3 lp;
+    if (img == 1u) {
+        // as written (pt_shade.compute:38-44): the record's ray origin + bias * its
+        // direction.  Record j's ray: j = 0 (light point, 0), j = 1 (light point,
+        // d0), j >= 2 (pos_{j-1} + bounce_bias * out_{j-1}, out_{j-1})
+        // (lbb_construction.compute:229-235, 391-395); din_j = that direction.
+        const float4 pp = lv[3 * (j >= 1u ? j - 1u : 0u)];
+        const v3 org = j >= 2u ? mk(pp.x, pp.y, pp.z) + dj * bounce_bias : mk(pp.x, pp.y, pp.z);
+        lp = org + dj * bias;
+    } else {  // 2: the vertex itself, pulled back like the hit connections' target
+        lp = mk(pv.x, pv.y, pv.z) - dj * bounce_bias;
+    }
+    const v3 d = lp - sensor;
+    t = length(d);
+    dir = normalize(d);
+    const float ct = dot(cn, dir);
+    float we = 1.0f / ((((a * ct) * ct) * ct) * ct);
+    const float npdf = (t * t) / fabsf(dot(cn, dir));
+    if (ct <= 0.0f) we = 0.0f;
+    cj = ((mk(hc.x, hc.y, hc.z) * we) / npdf) / (float)(j + 1);
+    return true;
+}
+
 // shadeBDPTImagePlane (pt_shade.compute:17-97; the oracle's bdpt_image_plane):
 // every path connects the vertices of one subpath to its own point on the
 // sensor before bounce 0.  The connections are a group of shadow records like
@@ -731,9 +771,9 @@ __global__ __launch_bounds__(256) void k_img_connect(DevScene S, Wave Wv) {
     uint32_t li = (uint32_t)((float)bd.L * draw_u01(key, dim_of(IMG_BOUNCE, P_LIGHT_SEL)));
     sp = sp < bd.Ns ? sp : bd.Ns - 1u;
     li = li < bd.L ? li : bd.L - 1u;
-    const v3 axs = ld3(cam.axis_x) * cam.pixel_size, ays = ld3(cam.axis_y) * cam.pixel_size;
-    const float a = length(cross(ays * (float)Wv.H, axs * (float)Wv.W));
-    const v3 cn = normalize(cross(ays, axs));
+    float a;
+    v3 cn;
+    img_sensor(cam, Wv.W, Wv.H, a, cn);
     const uint32_t q = fr * Wv.n_samples + s_local;
     const float4* lv = bd.lv + 3 * ((((size_t)q * bd.Ns + sp) * bd.L + li) * bd.J);
     // two passes over the vertices: count the non-zero terms, then write the group
@@ -746,30 +786,9 @@ __global__ __launch_bounds__(256) void k_img_connect(DevScene S, Wave Wv) {
         }
         bool head = true;
         for (uint32_t j = 0; j < bd.J; ++j) {
-            const float4 pv = lv[3 * j];
-            if (pv.w == 0.0f) continue;
-            const float4 din = lv[3 * j + 1], hc = lv[3 * j + 2];
-            const v3 dj = mk(din.x, din.y, din.z);
-            v3 lp;
-            if (bd.img == 1u) {
-                // as written (pt_shade.compute:38-44): the record's ray origin + bias * its
-                // direction.  Record j's ray: j = 0 (light point, 0), j = 1 (light point,
-                // d0), j >= 2 (pos_{j-1} + bounce_bias * out_{j-1}, out_{j-1})
-                // (lbb_construction.compute:229-235, 391-395); din_j = that direction.
-                const float4 pp = lv[3 * (j >= 1u ? j - 1u : 0u)];
-                const v3 org = j >= 2u ? mk(pp.x, pp.y, pp.z) + dj * bd.bounce_bias : mk(pp.x, pp.y, pp.z);
-                lp = org + dj * bd.bias;
-            } else {  // 2: the vertex itself, pulled back like the hit connections' target
-                lp = mk(pv.x, pv.y, pv.z) - dj * bd.bounce_bias;
-            }
-            const v3 d = lp - sensor;
-            const float t = length(d);
-            const v3 dir = normalize(d);
-            const float ct = dot(cn, dir);
-            float we = 1.0f / ((((a * ct) * ct) * ct) * ct);
-            const float npdf = (t * t) / fabsf(dot(cn, dir));
-            if (ct <= 0.0f) we = 0.0f;
-            const v3 cj = ((mk(hc.x, hc.y, hc.z) * we) / npdf) / (float)(j + 1);
+            v3 dir, cj;
+            float t;
+            if (!img_connection(bd.img, bd.bias, bd.bounce_bias, lv, j, sensor, a, cn, dir, t, cj)) continue;
             if (cj.x == 0.0f && cj.y == 0.0f && cj.z == 0.0f) continue;  // cannot change the sum
             if (pass == 0) {
                 ++nv;

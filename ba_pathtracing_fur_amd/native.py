@@ -215,10 +215,11 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_tonemap_log_sum", "khp_set_camera", "khp_debug_comm_wait", "khp_fur_params_defaults",
             "khp_fur_count", "khp_gen_fur", "khp_gen_fur_device", "khp_debug_surface", "khp_debug_bsdf_sample",
             "khp_debug_bsdf_eval", "khp_debug_light_dir", "khp_debug_light_isect", "khp_hair_lobes_defaults",
-            "khp_set_hair_lobes", "khp_get_hair_lobes", "khp_debug_hair_sample", "khp_render_aov"]
+            "khp_set_hair_lobes", "khp_get_hair_lobes", "khp_debug_hair_sample", "khp_render_aov",
+            "khp_debug_light_paths", "khp_debug_bdpt_connect", "khp_debug_img_connect"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _lib = None
 
@@ -326,6 +327,12 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
                                         P(c_float), P(c_float)]),
         "khp_debug_light_isect": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_float), P(c_float), P(c_uint8),
                                           P(c_float), P(c_float)]),
+        "khp_debug_light_paths": (c_int, [c_void_p, c_uint32, c_uint32, P(c_float)]),
+        "khp_debug_bdpt_connect": (c_int, [c_void_p, c_uint32, P(c_float), P(c_float), P(c_uint32), P(c_int32),
+                                           P(c_uint32), P(c_float), P(c_uint8), P(c_uint8), P(c_float), P(c_float),
+                                           P(c_float), P(c_float)]),
+        "khp_debug_img_connect": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, P(c_float), P(c_uint32), P(c_float),
+                                          P(c_float), P(c_uint8), P(c_float), P(c_float), P(c_float)]),
         "khp_host_build": (c_int, [P(SceneDesc), P(c_uint32), P(c_uint32), P(c_float), P(c_int32), P(c_int32),
                                    P(c_int32), P(c_float), P(c_float)]),
     }

@@ -459,6 +459,53 @@ class HipContext:
                                                          N.fptr(r["t"]), N.fptr(r["emit"])), "khp_debug_light_isect")
         return r
 
+    # ---- ABI 17 queries of the light-path variant (test hooks) ----
+    def debug_light_paths(self, k, seed=0x4B49524B):
+        """khp_debug_light_paths: the subpaths of sample index k as the renderer's own kernel
+        traces them -> [light_paths, n_lights, vertices, 10] (valid, pos, din, hit colour)."""
+        prm = N.BdptParams()
+        N.check(self.lib, self.lib.khp_get_bdpt(self.ptr, ctypes.byref(prm)), "khp_get_bdpt")
+        nl = len(self._scene.lights) if self._scene is not None else 0
+        shape = (int(prm.light_paths), nl, int(prm.vertices), 10)
+        out = np.zeros(max(1, int(np.prod(shape))), np.float32)
+        N.check(self.lib, self.lib.khp_debug_light_paths(self.ptr, int(seed), int(k), N.fptr(out)),
+                "khp_debug_light_paths")
+        return out[:int(np.prod(shape))].reshape(shape)
+
+    def debug_bdpt_connect(self, orig, direction, bounce, light, j, vertex):
+        """khp_debug_bdpt_connect on n items -> hit, accepted, connection ray (o, d), tmax, cj."""
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+        n = len(o)
+        b = np.ascontiguousarray(bounce, np.uint32).reshape(-1)
+        li = np.ascontiguousarray(light, np.int32).reshape(-1)
+        jj = np.ascontiguousarray(j, np.uint32).reshape(-1)
+        v = np.ascontiguousarray(vertex, np.float32).reshape(-1, 10)
+        up = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+        bp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        r = {"hit": np.empty(n, np.uint8), "accepted": np.empty(n, np.uint8), "o": np.empty((n, 3), np.float32),
+             "d": np.empty((n, 3), np.float32), "tmax": np.empty(n, np.float32), "cj": np.empty((n, 3), np.float32)}
+        N.check(self.lib, self.lib.khp_debug_bdpt_connect(
+            self.ptr, n, N.fptr(o), N.fptr(d), up(b), li.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), up(jj),
+            N.fptr(v), bp(r["hit"]), bp(r["accepted"]), N.fptr(r["o"]), N.fptr(r["d"]), N.fptr(r["tmax"]),
+            N.fptr(r["cj"])), "khp_debug_bdpt_connect")
+        return r
+
+    def debug_img_connect(self, width, height, sensor, j, prev, cur):
+        """khp_debug_img_connect on n items of a width x height frame -> accepted, d, t, cj."""
+        s = np.ascontiguousarray(sensor, np.float32).reshape(-1, 3)
+        n = len(s)
+        jj = np.ascontiguousarray(j, np.uint32).reshape(-1)
+        pv = np.ascontiguousarray(prev, np.float32).reshape(-1, 10)
+        cv = np.ascontiguousarray(cur, np.float32).reshape(-1, 10)
+        r = {"accepted": np.empty(n, np.uint8), "d": np.empty((n, 3), np.float32), "t": np.empty(n, np.float32),
+             "cj": np.empty((n, 3), np.float32)}
+        N.check(self.lib, self.lib.khp_debug_img_connect(
+            self.ptr, int(width), int(height), n, N.fptr(s), jj.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+            N.fptr(pv), N.fptr(cv), r["accepted"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), N.fptr(r["d"]),
+            N.fptr(r["t"]), N.fptr(r["cj"])), "khp_debug_img_connect")
+        return r
+
     def debug_queues(self):
         """The extension rays and the shadow rays (o, d, t_max) of bounce
         khp_ctx_params.dump_bounce of the last synchronous render."""

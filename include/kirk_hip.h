@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define KHP_ABI_VERSION 16
+#define KHP_ABI_VERSION 17
 
 typedef struct khp_ctx khp_ctx;
 
@@ -717,6 +717,41 @@ khp_status khp_debug_light_dir(khp_ctx* ctx, uint32_t n, const int32_t* light, c
  * (0 / 1), t [n] (0 on a miss), the emitted colour [n][3]. */
 khp_status khp_debug_light_isect(khp_ctx* ctx, uint32_t n, const int32_t* light, const float* orig,
                                  const float* dir, uint8_t* hit, float* t, float* emitted);
+/* ---- ABI 17: queries of the light-path variant (test hooks) -----
+ * Same rules as the ABI 15 queries: one item per thread, the device functions
+ * the renderer calls, every index and count checked on the host (KHP_EINVAL,
+ * nothing launched), scratch of their own -- no framebuffer, statistics, frame
+ * in flight or render-ahead state is touched.  They use the context's current
+ * khp_bdpt_params -- light_paths, vertices, bias, bounce_bias, min_pdf and
+ * image_plane -- whether or not the variant is enabled.  A vertex record is 10
+ * floats: valid (0 / 1), position, incoming direction, hit colour.
+ *
+ * khp_debug_light_paths: the renderer's light-subpath kernel itself for the one
+ * sample index k and the render seed `seed`: out is
+ * [light_paths][n_lights][vertices][10]; invalid vertices are all zero.
+ * KHP_EINVAL for a scene without lights or when light_paths * n_lights *
+ * vertices exceeds 2^20. */
+khp_status khp_debug_light_paths(khp_ctx* ctx, uint32_t seed, uint32_t k, float* out);
+/* One hit connection per item: the closest hit of the camera ray (orig, dir
+ * [n][3], the direction normalised as KIRK::Ray does) and the surface there,
+ * then the connection at bounce[i] (<= 4095) to vertex[i] (a record, its index
+ * j[i] < 16) of a subpath of light[i].  Outputs: hit [n] (0: the camera ray
+ * missed), accepted [n] (0: a miss or an invalid vertex; the rest of the item
+ * is then zero), the connection ray's origin and direction [n][3], t_max [n]
+ * and the contribution c_j [n][3].  No occlusion test. */
+khp_status khp_debug_bdpt_connect(khp_ctx* ctx, uint32_t n, const float* orig, const float* dir,
+                                  const uint32_t* bounce, const int32_t* light, const uint32_t* j,
+                                  const float* vertex, uint8_t* hit, uint8_t* accepted, float* ray_orig,
+                                  float* ray_dir, float* tmax, float* cj);
+/* One image-plane connection per item in a width x height frame (both enter the
+ * sensor area): from sensor[i] ([n][3]) to the target of record j[i] (< 16),
+ * given records j - 1 (prev, ignored for j = 0) and j (cur), [n][10] each,
+ * with the context's image_plane (1 or 2; 0 is KHP_EINVAL).  Outputs: accepted
+ * [n] (0: an invalid vertex, the rest zero), the visibility ray's direction
+ * [n][3], its length t [n] and the term c_j [n][3].  No occlusion test. */
+khp_status khp_debug_img_connect(khp_ctx* ctx, uint32_t width, uint32_t height, uint32_t n, const float* sensor,
+                                 const uint32_t* j, const float* prev, const float* cur, uint8_t* accepted,
+                                 float* dir, float* t, float* cj);
 /* ABI 13, test hook for the bounded device waits of a rank: builds
  * one RCCL-operation bracket (events `pre` / `post`, as around an ncclSend /
  * ncclRecv) on the context stream around a gate kernel that spins until

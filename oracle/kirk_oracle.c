@@ -1603,6 +1603,37 @@ static int build_light_paths(struct ko_ctx* c, uint32_t seed, uint32_t k0, uint3
     return KHP_OK;
 }
 
+/* One image-plane connection (pt_shade.compute:38-92): the visibility ray from the
+ * sensor point towards the target of record j, its length and the importance-weighted
+ * term.  prev = record j-1 (record 0 for j = 0).  Returns 0 for an invalid vertex. */
+static int img_connection(const khp_bdpt_params* bd, const lvert_t* prev, const lvert_t* cur, uint32_t j, v3 sensor,
+                          float a, v3 cn, ray_t* vis, float* t_out, v3* cj) {
+    if (!cur->valid) return 0;
+    v3 lp;
+    if (bd->image_plane == 1) {
+        /* as written (pt_shade.compute:38-44): pos = light_bounce.ray.origin, target
+         * pos + debug.bias * light_bounce.ray.direction.  Record j's ray
+         * (lbb_construction.compute:229-235, 391-395): j = 0 (light point, 0),
+         * j = 1 (light point, d0), j >= 2 (pos_{j-1} + bounce_bias * out_{j-1},
+         * out_{j-1}); din_j holds that direction (0 for j = 0). */
+        v3 org = j >= 2 ? vadd(prev->pos, vscale(cur->din, bd->bounce_bias)) : prev->pos;
+        lp = vadd(org, vscale(cur->din, bd->bias));
+    } else {   /* 2: the vertex itself, pulled back like the hit connections' target */
+        lp = vsub(cur->pos, vscale(cur->din, bd->bounce_bias));
+    }
+    v3 d = vsub(lp, sensor);
+    float t = length(d);
+    vis->o = sensor;
+    vis->d = normalize(d);
+    float ct = dot(cn, vis->d);
+    float we = 1.0f / ((((a * ct) * ct) * ct) * ct);
+    float npdf = (t * t) / fabsf(dot(cn, vis->d));
+    if (ct <= 0.0f) we = 0.0f;
+    *cj = vdivs(vdivs(vscale(cur->hc, we), npdf), (float)(j + 1));
+    *t_out = t;
+    return 1;
+}
+
 /* shadeBDPTImagePlane (pt_shade.compute:17-97): connect every valid vertex of one
  * subpath (chosen with the sample's own draws at dims IMG_DIM) to the sample's
  * point on the sensor; the unoccluded importance-weighted terms, summed in
@@ -1622,29 +1653,10 @@ static v3 bdpt_image_plane(const struct ko_ctx* c, uint32_t W, uint32_t H, v3 se
     v3 cn = normalize(cross(ays, axs));                                        /* camera normal */
     const lvert_t* v = c->lv + (((size_t)(k - c->lv_k0) * Ns + sp) * L + li) * J;
     for (uint32_t j = 0; j < J; ++j) {
-        if (!v[j].valid) continue;
-        v3 lp;
-        if (bd->image_plane == 1) {
-            /* as written (pt_shade.compute:38-44): pos = light_bounce.ray.origin, target
-             * pos + debug.bias * light_bounce.ray.direction.  Record j's ray
-             * (lbb_construction.compute:229-235, 391-395): j = 0 (light point, 0),
-             * j = 1 (light point, d0), j >= 2 (pos_{j-1} + bounce_bias * out_{j-1},
-             * out_{j-1}); din_j holds that direction (0 for j = 0). */
-            v3 org = j >= 2 ? vadd(v[j - 1].pos, vscale(v[j].din, bd->bounce_bias)) : v[j >= 1 ? j - 1 : 0].pos;
-            lp = vadd(org, vscale(v[j].din, bd->bias));
-        } else {   /* 2: the vertex itself, pulled back like the hit connections' target */
-            lp = vsub(v[j].pos, vscale(v[j].din, bd->bounce_bias));
-        }
-        v3 d = vsub(lp, sensor);
-        float t = length(d);
         ray_t vis;
-        vis.o = sensor;
-        vis.d = normalize(d);
-        float ct = dot(cn, vis.d);
-        float we = 1.0f / ((((a * ct) * ct) * ct) * ct);
-        float npdf = (t * t) / fabsf(dot(cn, vis.d));
-        if (ct <= 0.0f) we = 0.0f;
-        v3 cj = vdivs(vdivs(vscale(v[j].hc, we), npdf), (float)(j + 1));
+        float t;
+        v3 cj;
+        if (!img_connection(bd, &v[j >= 1 ? j - 1 : 0], &v[j], j, sensor, a, cn, &vis, &t, &cj)) continue;
         int occ = bvh_any(c, &vis, t, NULL);
         if (!occ) {
             for (uint32_t i = 0; i < c->n_lights; ++i) {
@@ -1656,6 +1668,23 @@ static v3 bdpt_image_plane(const struct ko_ctx* c, uint32_t W, uint32_t H, v3 se
     }
     /* added like a connection group's term: (0 + dl * 1) + 0 */
     return vadd(vadd(V(0.0f, 0.0f, 0.0f), vmul(dl, V(1.0f, 1.0f, 1.0f))), V(0.0f, 0.0f, 0.0f));
+}
+
+/* One connection of a camera hit to vertex j of a subpath (pt_shade.compute:150-199):
+ * the connection ray, its length and the contribution it adds when unoccluded.
+ * Returns 0 for an invalid vertex. */
+static int bd_connection(const khp_bdpt_params* bd, const lvert_t* v, uint32_t j, const light_t* Lt, const shade_ctx_t* s,
+                         v3 loc, v3 rd, uint32_t b, ray_t* sh, float* t_max, v3* cj) {
+    if (!v->valid) return 0;
+    v3 lp = vsub(v->pos, vscale(v->din, bd->bounce_bias));
+    v3 lc = j == 0 ? vscale(Lt->color, gl_ang_att(Lt, vsub(lp, loc))) : Lt->color;
+    sh->o = vadd(loc, vscale(s->n, bd->bias));
+    sh->d = normalize(vsub(lp, loc));
+    *t_max = length(vsub(lp, sh->o));
+    lc = vscale(lc, fabsf(dot(sh->d, s->n)));
+    lc = vmul(lc, bsdf_eval(s, vneg(rd), sh->d));
+    *cj = vdivs(vmul(v->hc, lc), (float)(j + 1 + b));
+    return 1;
 }
 
 /* pt_shade.compute:146-201: connect the hit to every valid vertex of one subpath
@@ -1674,16 +1703,10 @@ static v3 bdpt_connect(const struct ko_ctx* c, const shade_ctx_t* s, v3 loc, con
     const light_t* Lt = &c->lights[li];
     const lvert_t* v = c->lv + (((size_t)(k - c->lv_k0) * Ns + sp) * L + li) * J;
     for (uint32_t j = 0; j < J; ++j) {
-        if (!v[j].valid) continue;
-        v3 lp = vsub(v[j].pos, vscale(v[j].din, bd->bounce_bias));
-        v3 lc = j == 0 ? vscale(Lt->color, gl_ang_att(Lt, vsub(lp, loc))) : Lt->color;
         ray_t sh;
-        sh.o = vadd(loc, vscale(s->n, bd->bias));
-        sh.d = normalize(vsub(lp, loc));
-        float t_max = length(vsub(lp, sh.o));
-        lc = vscale(lc, fabsf(dot(sh.d, s->n)));
-        lc = vmul(lc, bsdf_eval(s, vneg(ray->d), sh.d));
-        v3 cj = vdivs(vmul(v[j].hc, lc), (float)(j + 1 + b));
+        float t_max;
+        v3 cj;
+        if (!bd_connection(bd, &v[j], j, Lt, s, loc, ray->d, b, &sh, &t_max, &cj)) continue;
         int occ = bvh_any(c, &sh, t_max, NULL);
         if (!occ) {   /* intersectsAnyWithLights (inc_light.compute:508-535); the sun is never hit */
             for (uint32_t i = 0; i < c->n_lights; ++i) {
@@ -2225,6 +2248,90 @@ int ko_light_isect(ko_ctx* c, uint32_t n, const int32_t* li, const float* orig, 
         hit[i] = (uint8_t)h;
         t_out[i] = h ? t : 0.0f;
         st3(emit + 3 * (size_t)i, light_emit(&c->lights[li[i]], r.d));
+    }
+    return KHP_OK;
+}
+
+/* ---- counterparts of the ABI 17 device queries (khp_debug_bdpt_connect / _img_connect) ---- */
+static lvert_t lvert_from10(const float* r) {
+    lvert_t v;
+    v.valid = r[0] != 0.0f;
+    v.pos = ld3(r + 1);
+    v.din = ld3(r + 4);
+    v.hc = ld3(r + 7);
+    return v;
+}
+
+/* bdpt_connect's per-vertex arithmetic on n items: the closest hit of the camera ray
+ * (orig, dir), then its connection at bounce b[i] to the vertex record vert10[i]
+ * (index j[i]) of a subpath of light li[i].  No occlusion test.  A miss or an invalid
+ * vertex leaves the item's outputs zero. */
+int ko_bdpt_connect_n(ko_ctx* c, uint32_t n, const float* orig, const float* dir, const uint32_t* b, const int32_t* li,
+                      const uint32_t* j, const float* vert10, uint8_t* hit, uint8_t* accepted, float* ray_orig,
+                      float* ray_dir, float* tmax, float* cj) {
+    if (!c) return KHP_EINVAL;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (li[i] < 0 || (uint32_t)li[i] >= c->n_lights || j[i] >= 16u || b[i] > 4095u) return KHP_EINVAL;
+        ray_t r = make_ray(ld3(orig + 3 * (size_t)i), ld3(dir + 3 * (size_t)i));
+        hit_t h;
+        hit[i] = accepted[i] = 0;
+        memset(ray_orig + 3 * (size_t)i, 0, 3 * sizeof(float));
+        memset(ray_dir + 3 * (size_t)i, 0, 3 * sizeof(float));
+        memset(cj + 3 * (size_t)i, 0, 3 * sizeof(float));
+        tmax[i] = 0.0f;
+        if (!bvh_closest(c, &r, &h, NULL)) continue;
+        hit[i] = 1;
+        const obj_t* o = &c->obj[h.obj];
+        v3 nrm = obj_normal(o, &r, &h), loc = follow(&r, h.lambda);
+        const khp_material* m = &c->mats[o->mat];
+        khp_material mtx;
+        if (c->textured) {
+            float tu, tv;
+            obj_tcoord(o, &h, loc, &tu, &tv);
+            material_at(c, o->mat, tu, tv, &mtx);
+            m = &mtx;
+        }
+        shade_ctx_t s; s.obj = o; s.m = m; s.n = nrm;
+        const lvert_t v = lvert_from10(vert10 + 10 * (size_t)i);
+        ray_t sh;
+        float tm;
+        v3 col;
+        if (!bd_connection(&c->bd, &v, j[i], &c->lights[li[i]], &s, loc, r.d, b[i], &sh, &tm, &col)) continue;
+        accepted[i] = 1;
+        st3(ray_orig + 3 * (size_t)i, sh.o);
+        st3(ray_dir + 3 * (size_t)i, sh.d);
+        tmax[i] = tm;
+        st3(cj + 3 * (size_t)i, col);
+    }
+    return KHP_OK;
+}
+
+/* bdpt_image_plane's per-vertex arithmetic on n items of a width x height frame: the
+ * visibility ray from sensor[i] towards the target of record j[i] (prev10 = record
+ * j - 1, cur10 = record j), its length and the term.  image_plane 1 or 2 (ko_set_bdpt). */
+int ko_img_connect_n(ko_ctx* c, uint32_t width, uint32_t height, uint32_t n, const float* sensor, const uint32_t* j,
+                     const float* prev10, const float* cur10, uint8_t* accepted, float* dir, float* t_out, float* cj) {
+    if (!c || width == 0 || height == 0 || (c->bd.image_plane != 1 && c->bd.image_plane != 2)) return KHP_EINVAL;
+    const khp_camera* cam = &c->cam;
+    v3 axs = vscale(ld3(cam->axis_x), cam->pixel_size), ays = vscale(ld3(cam->axis_y), cam->pixel_size);
+    float a = length(cross(vscale(ays, (float)height), vscale(axs, (float)width)));
+    v3 cn = normalize(cross(ays, axs));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (j[i] >= 16u) return KHP_EINVAL;
+        const lvert_t pv = lvert_from10(prev10 + 10 * (size_t)i), cv = lvert_from10(cur10 + 10 * (size_t)i);
+        ray_t vis;
+        float t;
+        v3 col;
+        accepted[i] = 0;
+        memset(dir + 3 * (size_t)i, 0, 3 * sizeof(float));
+        memset(cj + 3 * (size_t)i, 0, 3 * sizeof(float));
+        t_out[i] = 0.0f;
+        if (!img_connection(&c->bd, j[i] >= 1 ? &pv : &cv, &cv, j[i], ld3(sensor + 3 * (size_t)i), a, cn, &vis, &t, &col))
+            continue;
+        accepted[i] = 1;
+        st3(dir + 3 * (size_t)i, vis.d);
+        t_out[i] = t;
+        st3(cj + 3 * (size_t)i, col);
     }
     return KHP_OK;
 }

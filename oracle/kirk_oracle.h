@@ -112,6 +112,15 @@ int ko_light_dir(ko_ctx* c, uint32_t n, const int32_t* li, const float* p, const
 int ko_light_isect(ko_ctx* c, uint32_t n, const int32_t* li, const float* orig, const float* dir, uint8_t* hit,
                    float* t_out, float* emit);
 
+/* Counterparts of the ABI 17 device queries (khp_debug_bdpt_connect, khp_debug_img_connect;
+ * khp_debug_light_paths' is ko_light_paths): the same arguments and outputs, with the
+ * parameters of ko_set_bdpt.  They call the per-vertex functions the renders call. */
+int ko_bdpt_connect_n(ko_ctx* c, uint32_t n, const float* orig, const float* dir, const uint32_t* b, const int32_t* li,
+                      const uint32_t* j, const float* vert10, uint8_t* hit, uint8_t* accepted, float* ray_orig,
+                      float* ray_dir, float* tmax, float* cj);
+int ko_img_connect_n(ko_ctx* c, uint32_t width, uint32_t height, uint32_t n, const float* sensor, const uint32_t* j,
+                     const float* prev10, const float* cur10, uint8_t* accepted, float* dir, float* t_out, float* cj);
+
 /* Output stage (kirk_tonemap.c): Texture::setPixel byte conversion and
  * Tonemapper::map, sequential in KIRK's order. */
 void ko_tonemap_defaults(khp_tonemap* t);

@@ -83,6 +83,11 @@ def load():
                                  P(c_float)]),
         "ko_light_isect": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_float), P(c_float), P(c_uint8), P(c_float),
                                    P(c_float)]),
+        "ko_bdpt_connect_n": (c_int, [c_void_p, c_uint32, P(c_float), P(c_float), P(c_uint32), P(c_int32), P(c_uint32),
+                                      P(c_float), P(c_uint8), P(c_uint8), P(c_float), P(c_float), P(c_float),
+                                      P(c_float)]),
+        "ko_img_connect_n": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, P(c_float), P(c_uint32), P(c_float),
+                                     P(c_float), P(c_uint8), P(c_float), P(c_float), P(c_float)]),
         "ko_to_rgba8": (None, [c_uint32, P(c_float), P(c_uint8)]),
         "ko_tonemap": (c_int, [c_uint32, c_uint32, P(c_float), c_void_p, P(c_float), P(c_float), P(c_float)]),
     }
@@ -290,6 +295,44 @@ class Oracle:
                                      _fp(r["t"]), _fp(r["emit"]))
         if rc != 0:
             raise ValueError(f"ko_light_isect failed ({rc})")
+        return r
+
+    # ---- counterparts of the ABI 17 device queries (same names and keys as HipContext.debug_*) ----
+    def debug_light_paths(self, k, seed=0x4B49524B):
+        return self.light_paths(k, seed)
+
+    def debug_bdpt_connect(self, orig, direction, bounce, light, j, vertex):
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+        n = len(o)
+        b = np.ascontiguousarray(bounce, np.uint32).reshape(-1)
+        li = np.ascontiguousarray(light, np.int32).reshape(-1)
+        jj = np.ascontiguousarray(j, np.uint32).reshape(-1)
+        v = np.ascontiguousarray(vertex, np.float32).reshape(-1, 10)
+        up = lambda a: a.ctypes.data_as(POINTER(c_uint32))
+        bp = lambda a: a.ctypes.data_as(POINTER(c_uint8))
+        r = {"hit": np.empty(n, np.uint8), "accepted": np.empty(n, np.uint8), "o": np.empty((n, 3), np.float32),
+             "d": np.empty((n, 3), np.float32), "tmax": np.empty(n, np.float32), "cj": np.empty((n, 3), np.float32)}
+        rc = self.lib.ko_bdpt_connect_n(self.ptr, n, _fp(o), _fp(d), up(b), _ip(li), up(jj), _fp(v), bp(r["hit"]),
+                                        bp(r["accepted"]), _fp(r["o"]), _fp(r["d"]), _fp(r["tmax"]), _fp(r["cj"]))
+        if rc != 0:
+            raise ValueError(f"ko_bdpt_connect_n failed ({rc})")
+        return r
+
+    def debug_img_connect(self, width, height, sensor, j, prev, cur):
+        s = np.ascontiguousarray(sensor, np.float32).reshape(-1, 3)
+        n = len(s)
+        jj = np.ascontiguousarray(j, np.uint32).reshape(-1)
+        pv = np.ascontiguousarray(prev, np.float32).reshape(-1, 10)
+        cv = np.ascontiguousarray(cur, np.float32).reshape(-1, 10)
+        r = {"accepted": np.empty(n, np.uint8), "d": np.empty((n, 3), np.float32), "t": np.empty(n, np.float32),
+             "cj": np.empty((n, 3), np.float32)}
+        rc = self.lib.ko_img_connect_n(self.ptr, int(width), int(height), n, _fp(s),
+                                       jj.ctypes.data_as(POINTER(c_uint32)), _fp(pv), _fp(cv),
+                                       r["accepted"].ctypes.data_as(POINTER(c_uint8)), _fp(r["d"]), _fp(r["t"]),
+                                       _fp(r["cj"]))
+        if rc != 0:
+            raise ValueError(f"ko_img_connect_n failed ({rc})")
         return r
 
 

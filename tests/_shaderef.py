@@ -538,9 +538,10 @@ def cone_normal(cs, c, o, d, dtype=np.float64):
         return unit(grad).astype(dt), t.astype(dt)
 
 
-def triangle_normal(tri_v, tri_n, k, o, d, dtype=np.float64):
+def triangle_normal(tri_v, tri_n, k, o, d, dtype=np.float64, with_t=False):
     """Shading normal of triangle k at the hit of ray (o, d): the barycentric blend of
-    its unit vertex normals (Triangle.cpp:244-248), normalised."""
+    its unit vertex normals (Triangle.cpp:244-248), normalised.  with_t: also the hit
+    distance against the same (KIRK's) edges."""
     dt = dtype
     v, vn = np.asarray(tri_v, dt)[k].copy(), np.asarray(tri_n, dt)[k].copy()
     o, d = np.asarray(o, dt), np.asarray(d, dt)
@@ -572,6 +573,8 @@ def triangle_normal(tri_v, tri_n, k, o, d, dtype=np.float64):
         b1 = dot(tv, pv) / det
         b2 = dot(d, cross(tv, e1)) / det
         blend = unit(vn[:, 0]) * (1 - b1 - b2)[:, None] + unit(vn[:, 1]) * b1[:, None] + unit(vn[:, 2]) * b2[:, None]
+        if with_t:
+            return unit(blend).astype(dt), (dot(e2, cross(tv, e1)) / det).astype(dt)
         return unit(blend).astype(dt)
 
 

@@ -1,7 +1,7 @@
 """The C-ABI drop-in boundary (include/kirk_hip.h): library loads, exports what the
 header declares, registries mirror KIRK's factories, errors are loud.  CPU only (khp_create is
 checked to *fail* without a GPU), except the bad-argument cases of the ABI 15
-batch queries, which need a context (`gpu`).
+and ABI 17 batch queries, which need a context (`gpu`).
 """
 import ctypes
 import os
@@ -259,3 +259,107 @@ def test_debug_queries_refuse_bad_arguments(hip_ctx):
     fur = (1 << 0) | (1 << 9)
     assert bsdf(mask=fur, mat=3)[0][1](lib, c) == N.KHP_OK
     assert bsdf(mask=0x7)[0][1](lib, c) == N.KHP_EINVAL and "kinds_mask" in err()
+
+
+# ---- ABI 17: the queries of the light-path variant ------------------------------------------
+def _bdpt_query_calls(n, null=None, light=0, j=0, bounce=0, wh=(16, 12)):
+    """(name, callable(lib, ctx)) for khp_debug_bdpt_connect and khp_debug_img_connect on n items
+    (arrays of at most 4) and khp_debug_light_paths; `null` names one argument to omit."""
+    f = lambda *shape: np.zeros(shape, np.float32)
+    keep = []
+
+    def a(name, arr, t):
+        if name == null:
+            return ctypes.cast(None, ctypes.POINTER(t))
+        keep.append(arr)
+        return arr.ctypes.data_as(ctypes.POINTER(t))
+
+    m = min(max(n, 1), 4)
+    d = np.tile(np.float32([0, -1, 0]), (m, 1))
+    o = np.tile(np.float32([0, 0.5, 0]), (m, 1))
+    vert = np.tile(np.float32([1, 0, 0.9, 0, 0, -1, 0, 0.3, 0.3, 0.3]), (m, 1))
+    u32, i32, u8, fl = ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint8, ctypes.c_float
+    return [
+        ("khp_debug_bdpt_connect", lambda lib, c: lib.khp_debug_bdpt_connect(
+            c, n, a("orig", o, fl), a("dir", d, fl), a("bounce", np.full(m, bounce, np.uint32), u32),
+            a("light", np.full(m, light, np.int32), i32), a("j", np.full(m, j, np.uint32), u32), a("vertex", vert, fl),
+            a("hit", np.zeros(m, np.uint8), u8), a("accepted", np.zeros(m, np.uint8), u8), a("ray_orig", f(m, 3), fl),
+            a("ray_dir", f(m, 3), fl), a("tmax", f(m), fl), a("cj", f(m, 3), fl))),
+        ("khp_debug_img_connect", lambda lib, c: lib.khp_debug_img_connect(
+            c, wh[0], wh[1], n, a("sensor", o, fl), a("j", np.full(m, j, np.uint32), u32), a("prev", vert, fl),
+            a("cur", vert, fl), a("accepted", np.zeros(m, np.uint8), u8), a("dir", f(m, 3), fl), a("t", f(m), fl),
+            a("cj", f(m, 3), fl))),
+        ("khp_debug_light_paths", lambda lib, c: lib.khp_debug_light_paths(c, 1, 0, a("out", f(1 << 16), fl))),
+    ]
+
+
+BDPT_QUERY_ARGS = {"khp_debug_bdpt_connect": ["orig", "dir", "bounce", "light", "j", "vertex", "hit", "accepted", "ray_orig",
+                                              "ray_dir", "tmax", "cj"],
+                   "khp_debug_img_connect": ["sensor", "j", "prev", "cur", "accepted", "dir", "t", "cj"],
+                   "khp_debug_light_paths": ["out"]}
+
+
+def test_bdpt_queries_need_a_context():
+    lib = N.load_library()
+    for name, call in _bdpt_query_calls(4):
+        assert call(lib, None) == N.KHP_EINVAL, name
+        assert b"null" in lib.khp_last_error(), name
+
+
+@pytest.mark.gpu
+def test_bdpt_queries_refuse_bad_arguments(hip_ctx):
+    """Every index and count of the ABI 17 queries is checked on the host: nothing out of range reaches a kernel."""
+    from ba_pathtracing_fur_amd.pathtracer import HipContext
+    lib = N.load_library()
+    err = lambda: lib.khp_last_error().decode()
+    fresh = HipContext(0)                      # no scene yet
+    try:
+        for name, call in _bdpt_query_calls(4):
+            assert call(lib, fresh.ptr) == N.KHP_ENOTREADY and "khp_set_scene" in err(), name
+        fresh.set_scene(S.config1(8, 8))       # a scene, but no tree
+        for name, call in _bdpt_query_calls(4):
+            assert call(lib, fresh.ptr) == N.KHP_ENOTREADY and "khp_build_accel" in err(), name
+    finally:
+        fresh.close()
+    sd = S.config2(8, 8, n_strands=20)         # 1 light
+    hip_ctx.set_scene(sd)
+    hip_ctx.build_accel()
+    old = hip_ctx.set_bdpt(light_paths=16, vertices=4, image_plane=1)
+    c = hip_ctx.ptr
+    try:
+        for name, call in _bdpt_query_calls(4):
+            assert call(lib, c) == N.KHP_OK, (name, err())
+        for n in (0, (1 << 20) + 1, 0xFFFFFFFF):
+            for name, call in _bdpt_query_calls(n)[:2]:
+                assert call(lib, c) == N.KHP_EINVAL and "n must be" in err(), (name, n)
+        for k, (name, _) in enumerate(_bdpt_query_calls(4)):
+            for arg in BDPT_QUERY_ARGS[name]:
+                call = _bdpt_query_calls(4, null=arg)[k][1]
+                assert call(lib, c) == N.KHP_EINVAL and "null" in err(), (name, arg)
+        for bad in (-1, len(sd.lights), 1 << 30):
+            assert _bdpt_query_calls(4, light=bad)[0][1](lib, c) == N.KHP_EINVAL and "light" in err(), bad
+        for bad in (16, 1 << 31):
+            for name, call in _bdpt_query_calls(4, j=bad)[:2]:
+                assert call(lib, c) == N.KHP_EINVAL and "vertex index" in err(), (name, bad)
+        assert _bdpt_query_calls(4, bounce=4096)[0][1](lib, c) == N.KHP_EINVAL and "bounce" in err()
+        for wh in ((0, 12), (16, 0)):
+            assert _bdpt_query_calls(4, wh=wh)[1][1](lib, c) == N.KHP_EINVAL and "width" in err()
+        hip_ctx.set_bdpt(image_plane=0)
+        assert _bdpt_query_calls(4)[1][1](lib, c) == N.KHP_EINVAL and "image_plane" in err()
+        # light_paths x lights x vertices beyond 2^20 is refused before anything is allocated
+        hip_ctx.set_bdpt(light_paths=65536, vertices=16, image_plane=1)
+        assert 65536 * len(sd.lights) * 16 == 1 << 20
+        hip_ctx.set_bdpt(light_paths=65536, vertices=16)
+        two = S.config2(8, 8, n_strands=20)
+        two.lights = two.lights * 2            # 2 lights: 2^21 vertices
+        hip_ctx.set_scene(two)
+        hip_ctx.build_accel()
+        assert _bdpt_query_calls(4)[2][1](lib, c) == N.KHP_EINVAL and "2^20" in err()
+        none = S.config2(8, 8, n_strands=20)
+        none.lights = []
+        hip_ctx.set_scene(none)
+        hip_ctx.build_accel()
+        hip_ctx.set_bdpt(light_paths=16, vertices=4)
+        assert _bdpt_query_calls(4)[2][1](lib, c) == N.KHP_EINVAL and "no lights" in err()
+    finally:
+        hip_ctx.set_bdpt(**old)

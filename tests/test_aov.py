@@ -39,7 +39,8 @@ def test_symbol_is_exported_and_listed():
     header = open(os.path.join(ROOT, "include", "kirk_hip.h")).read()
     assert "khp_status khp_render_aov(khp_ctx* ctx, const khp_render_params* p, const khp_aov_buffers* out);" in header
     assert "#define KHP_AOV_TANGENT_IS_FRAME_V 1" in header
-    assert "#define KHP_ABI_VERSION 16" in header and N.ABI_VERSION == 16          # symbols are added, nothing moves
+    # khp_render_aov was added under ABI 16 (symbols added, nothing moved); 17 adds the light-path queries
+    assert "#define KHP_ABI_VERSION 17" in header and N.ABI_VERSION == 17
     assert "render_aov" in open(os.path.join(ROOT, "include", "kirk_hip.hpp")).read()
     assert callable(HipContext.render_aov)
     assert HipContext.AOV_CHANNELS == ("normal", "albedo", "tangent", "depth", "coverage", "object")

@@ -26,7 +26,7 @@ def test_defaults_and_layout():
     assert ctypes.sizeof(N.HairLobes) == 8
     assert (P.HAIR_LOBE_R, P.HAIR_LOBE_TT, P.HAIR_LOBE_TRT) == (1, 2, 4)
     assert {"HAIR_LOBE_R", "HAIR_LOBE_TT", "HAIR_LOBE_TRT"} <= set(P.__all__)
-    assert N.ABI_VERSION == 16 == lib.khp_abi_version()
+    assert N.ABI_VERSION == 17 == lib.khp_abi_version()   # 16 added these symbols; 17 the light-path queries
 
 
 def test_null_arguments_are_refused_without_a_device():
