@@ -275,6 +275,7 @@ __global__ void k_prep(Counters* c, ShadowQ* q, int cur) {
 #endif
 constexpr int RING = KHP_SH_RING;         // LDS ring entries per lane (3 x 4 B each), k_shadow
 constexpr int REFILL = 24;                // refill when >= REFILL lanes are idle
+constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;  // k_extend / k_shadow: the lane holds no unwritten result
 constexpr int TRAV_WAVES = KHP_SH_WAVES;  // __launch_bounds__ waves per SIMD, k_shadow
 constexpr int EXT_RING = KHP_EXT_RING;    // the same for k_extend
 constexpr int EXT_WAVES = KHP_EXT_WAVES;
@@ -510,19 +511,36 @@ __global__ __launch_bounds__(TRAV_BLOCK, WIDE ? EXT_WAVES_W : CAM ? CAM_WAVES : 
     Hit h;
     Cur c{0u, 0.0f, 0.0f, false};
     LeafCur lf{0u, 0u, 0.0f, 0.0f, 0.0f, 0.0f, -1};
-    bool has = false, exhausted = false;
-    uint32_t idx = 0, mode = 0u;
+    tr.fin = true;
+    bool exhausted = false;
+    // A lane walks a ray while mode != M_IDLE.  A finished lane is idle and keeps its
+    // result (h, it) and its queue slot (idx) in registers until the next refill
+    // or the end of the launch writes them out (NO_SLOT: nothing to write).
+    uint32_t idx = NO_SLOT, mode = M_IDLE;
     unsigned long long wit = 0, wbusy = 0;  // STATS: wave iterations, busy lanes
     uint32_t it = 0;  // this lane's iterations on its current ray (longest-first queues)
     Claimer cl;
     cl.init(Wv.cnt->fetch_ext, nf, nb, Wv.cap);
     constexpr int refill = WIDE ? KHP_REFILL_WIDE : CAM ? KHP_REFILL_CAM : KHP_REFILL_NARROW;
+    unsigned long long act = 0ull;  // lanes walking a ray (wave-uniform)
     for (;;) {
-        unsigned long long idle = __ballot(!has);
-        if (!exhausted && __popcll(idle) >= refill) {
-            uint32_t my;
-            const bool got = cl.claim(idle, my, exhausted);
-            if (!has && got && cl.phys(my, idx)) {
+        if (idx != NO_SLOT && mode == M_IDLE) {  // rays finished since the last refill
+            Wv.ht[idx] = h.t;
+            Wv.hslot[idx] = h.slot;
+            Wv.heavy[idx] = it > Wv.heavy_T ? 1 : 0;
+            if (CAM && Wv.pixheavy) mark_pixel(Wv, idx, it > Wv.heavy_T);
+            idx = NO_SLOT;
+        }
+        if (exhausted && act == 0) break;
+        if (!exhausted && 64 - __popcll(act) >= refill) {
+            uint32_t my, slot;
+            const bool has = mode != M_IDLE;
+            bool done = false;
+            const bool got = cl.claim(~act, my, done);
+            // the claim's state is the same in every lane: keep the flag in a scalar register
+            exhausted = __builtin_amdgcn_readfirstlane(done ? 1 : 0) != 0;
+            if (!has && got && cl.phys(my, slot)) {
+                idx = slot;
                 it = 0;
                 Ray r;
                 if (CAM) {
@@ -537,43 +555,28 @@ __global__ __launch_bounds__(TRAV_BLOCK, WIDE ? EXT_WAVES_W : CAM ? CAM_WAVES : 
                 h.slot = -1;
                 h.u = h.v = 0.0f;
                 lf.left = 0;
-                has = (STATS || !ray_has_nan(r)) && trav2_begin<STATS>(S, tr, h.t, stk, mode, c, lf, st);
-                if (!has) {  // missed the root box, or a NaN ray (no hit, see ray_has_nan)
-                    Wv.ht[idx] = h.t;
-                    Wv.hslot[idx] = -1;
-                    Wv.heavy[idx] = 0;
-                    if (CAM && Wv.pixheavy) mark_pixel(Wv, idx, false);
-                }
+                // missed the root box, or a NaN ray (no hit, see ray_has_nan): finished at once,
+                // written with the others at the top of the loop (t = FLT_MAX, slot -1, it = 0)
+                const bool go = (STATS || !ray_has_nan(r)) && trav2_begin<STATS>(S, tr, h.t, stk, mode, c, lf, st);
+                if (!go) mode = M_IDLE;
             }
         }
-        unsigned long long act = __ballot(has);
-        if (act == 0) {
-            if (exhausted) break;
-            continue;
-        }
+        act = wave_ballot(mode != M_IDLE);
+        if (act == 0) continue;
+        // Every lane runs the step: an idle lane fetches nothing, pushes and pops
+        // nothing and keeps its state, so the loop needs no per-lane branch region
+        // and one ballot per iteration.
         for (;;) {
             if (STATS) {
-                unsigned long long wm = __ballot(has && (mode == M_NODE || mode == M_LEAF));
+                unsigned long long wm = wave_ballot(mode == M_NODE || mode == M_LEAF);
                 ++wit;
                 wbusy += (uint32_t)__popcll(wm);
             }
-            if (has) {
-                bool occ_unused;
-                ++it;
-                const bool fin = WIDE ? iterw<false, STATS>(S, tr, h, 0.0f, stk, mode, c, lf, st, occ_unused)
-                                      : iter2<false, STATS>(S, tr, h, 0.0f, stk, mode, c, lf, st, occ_unused);
-                if (fin) {
-                    // the output addresses are formed here, not kept live through the loop
-                    uint32_t j = idx;
-                    asm volatile("" : "+v"(j));
-                    Wv.ht[j] = h.t;
-                    Wv.hslot[j] = h.slot;
-                    Wv.heavy[j] = it > Wv.heavy_T ? 1 : 0;
-                    if (CAM && Wv.pixheavy) mark_pixel(Wv, j, it > Wv.heavy_T);
-                    has = false;
-                }
-            }
-            act = __ballot(has);
+            bool occ_unused = false;
+            it += mode != M_IDLE ? 1u : 0u;
+            if (WIDE) iterw<false, STATS>(S, tr, h, 0.0f, stk, mode, c, lf, st, occ_unused);
+            else iter2<false, STATS>(S, tr, h, 0.0f, stk, mode, c, lf, st, occ_unused);
+            act = wave_ballot(mode != M_IDLE);
             if (act == 0 || (!exhausted && 64 - __popcll(act) >= refill)) break;
         }
     }
@@ -1466,17 +1469,32 @@ __global__ __launch_bounds__(TRAV_BLOCK, TRAV_WAVES) void k_shadow(DevScene S, W
     LeafCur lf{0u, 0u, 0.0f, 0.0f, 0.0f, 0.0f, -1};
     unsigned long long wit = 0, wbusy = 0;  // STATS: wave iterations, busy lanes
     float tmax = 0.0f;
-    uint32_t mode = 0u;
-    bool has = false, exhausted = false;
+    tr.fin = true;
+    // As in k_extend: a lane walks a ray while mode != M_IDLE; a finished lane keeps
+    // its answer (occ) and its queue slot (idx) until the next refill or the end of
+    // the launch writes them out (NO_SLOT: nothing to write).
+    uint32_t mode = M_IDLE;
+    bool exhausted = false, occ = false;
     Claimer cl;
     cl.init(Wv.shq->fetch, nf, nb, Wv.cap);
-    uint32_t idx = 0;
+    uint32_t idx = NO_SLOT;
+    unsigned long long act = 0ull;  // lanes walking a ray (wave-uniform)
     for (;;) {
-        unsigned long long idle = __ballot(!has);
-        if (!exhausted && __popcll(idle) >= REFILL) {
-            uint32_t my;
-            const bool got = cl.claim(idle, my, exhausted);
-            if (!has && got && cl.phys(my, idx)) {
+        if (idx != NO_SLOT && mode == M_IDLE) {  // rays finished since the last refill
+            Wv.vis[idx] = occ ? 1 : 0;
+            idx = NO_SLOT;
+        }
+        if (exhausted && act == 0) break;
+        if (!exhausted && 64 - __popcll(act) >= REFILL) {
+            uint32_t my, slot;
+            const bool has = mode != M_IDLE;
+            bool done = false;
+            const bool got = cl.claim(~act, my, done);
+            // the claim's state is the same in every lane: keep the flag in a scalar register
+            exhausted = __builtin_amdgcn_readfirstlane(done ? 1 : 0) != 0;
+            if (!has && got && cl.phys(my, slot)) {
+                idx = slot;
+                occ = false;
                 const float4* rec = Wv.sh + Wv.shs * (size_t)idx;
                 float4 a = rec[0], b = rec[1];
                 Ray r;
@@ -1485,37 +1503,30 @@ __global__ __launch_bounds__(TRAV_BLOCK, TRAV_WAVES) void k_shadow(DevScene S, W
                 tmax = a.w;
                 trav_setup(tr, r);
                 lf.left = 0;
+                // a ray answered here (the root box missed: not occluded) is finished at once
+                // and written with the others at the top of the loop
+                bool go;
                 if (!STATS && x_slab_nan(tr)) {  // the whole-tree walk, answered exactly (any_hit_x_nan)
-                    has = false;
-                    Wv.vis[idx] = any_hit_x_nan(S, r) ? 1 : 0;
+                    go = false;
+                    occ = any_hit_x_nan(S, r);
                 } else {
-                    has = trav2_begin<STATS>(S, tr, tmax, stk, mode, c, lf, st);
-                    if (!has) Wv.vis[idx] = 0;
+                    go = trav2_begin<STATS>(S, tr, tmax, stk, mode, c, lf, st);
                 }
+                if (!go) mode = M_IDLE;
             }
         }
-        unsigned long long act = __ballot(has);
-        if (act == 0) {
-            if (exhausted) break;
-            continue;
-        }
-        for (;;) {
+        act = wave_ballot(mode != M_IDLE);
+        if (act == 0) continue;
+        for (;;) {  // every lane runs the step; an idle lane changes nothing (k_extend)
             if (STATS) {
-                unsigned long long wm = __ballot(has && (mode == M_NODE || mode == M_LEAF));
+                unsigned long long wm = wave_ballot(mode == M_NODE || mode == M_LEAF);
                 ++wit;
                 wbusy += (uint32_t)__popcll(wm);
             }
-            if (has) {
-                bool occ = false;
-                Hit hu_{0.0f, -1, 0.0f, 0.0f};
-                const bool fin = WIDE ? iterw<true, STATS>(S, tr, hu_, tmax, stk, mode, c, lf, st, occ)
-                                      : iter2<true, STATS>(S, tr, hu_, tmax, stk, mode, c, lf, st, occ);
-                if (fin) {
-                    Wv.vis[idx] = occ ? 1 : 0;
-                    has = false;
-                }
-            }
-            act = __ballot(has);
+            Hit hu_{0.0f, -1, 0.0f, 0.0f};
+            if (WIDE) iterw<true, STATS>(S, tr, hu_, tmax, stk, mode, c, lf, st, occ);
+            else iter2<true, STATS>(S, tr, hu_, tmax, stk, mode, c, lf, st, occ);
+            act = wave_ballot(mode != M_IDLE);
             if (act == 0 || (!exhausted && 64 - __popcll(act) >= REFILL)) break;
         }
     }
@@ -5101,6 +5112,22 @@ __global__ void k_store_hits(DevScene S, uint32_t n, Wave Wv, float* t, int32_t*
     uv[2 * i + 1] = v;
 }
 
+// The persistent kernels write each queue slot's result once, from the lane that
+// traced it, some of them only at a later refill or at the end of the launch.  The
+// test hook fills the result columns with a sentinel byte first and counts, after
+// the launch, the slots of [0, n) that still hold it (a result never written) and
+// the slots of [n, cap) that no longer do (a write from a lane that had no ray).
+constexpr int TRACE_SENTINEL = 0xEE;   // no t (0xEEEEEEEE: -3.7e28), no slot (< -1), no flag (0 / 1)
+__global__ void k_check_sentinel(uint32_t n, uint32_t cap, const uint32_t* ht, const uint32_t* hslot, const uint8_t* vis,
+                                 int as_shadow, uint32_t* bad) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cap) return;
+    const uint32_t w = 0x01010101u * (uint32_t)TRACE_SENTINEL;
+    const bool left = as_shadow ? vis[i] == (uint8_t)TRACE_SENTINEL : (ht[i] == w || hslot[i] == w);
+    const bool touched = as_shadow ? vis[i] != (uint8_t)TRACE_SENTINEL : (ht[i] != w || hslot[i] != w);
+    if (i < n ? left : touched) atomicAdd(&bad[i < n ? 0 : 1], 1u);
+}
+
 // prm.trace_kernels -- 0: one-ray-per-thread kernels; 1: instrumented
 // persistent kernels (KIRK's visit counts); 2: production persistent kernels.
 static int trace_persistent(const khp_ctx* c) { return (int)c->prm.trace_kernels; }
@@ -5120,6 +5147,15 @@ static khp_status trace_persistent_run(khp_ctx* c, uint32_t n, const float* orig
     HIPCHK(hipMemsetAsync(w.cnt.p, 0, sizeof(Counters), c->stream));
     HIPCHK(hipMemsetAsync(w.shqb.p, 0, 2 * sizeof(ShadowQ), c->stream));
     Wave Wv = wave_view(c, w);
+    DevMem bad;
+    HIPCHK(bad.ensure(2 * sizeof(uint32_t)));
+    HIPCHK(hipMemsetAsync(bad.p, 0, 2 * sizeof(uint32_t), c->stream));
+    if (shadow) {
+        HIPCHK(hipMemsetAsync(Wv.vis, TRACE_SENTINEL, w.cap, c->stream));
+    } else {
+        HIPCHK(hipMemsetAsync(Wv.ht, TRACE_SENTINEL, w.cap * 4, c->stream));
+        HIPCHK(hipMemsetAsync(Wv.hslot, TRACE_SENTINEL, w.cap * 4, c->stream));
+    }
     hipLaunchKernelGGL(k_load_rays, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, o.as<float>(), d.as<float>(),
                        Wv, shadow ? 1 : 0, tm.as<float>());
     const bool prod = trace_persistent(c) == 2;
@@ -5147,12 +5183,25 @@ static khp_status trace_persistent_run(khp_ctx* c, uint32_t n, const float* orig
         HIPCHK(hipMemcpyAsync(obj_out, ob.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
         if (uv_out) HIPCHK(hipMemcpyAsync(uv_out, uv.p, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     }
+    const uint32_t cap = (uint32_t)w.cap;
+    hipLaunchKernelGGL(k_check_sentinel, dim3((cap + 255) / 256), dim3(256), 0, c->stream, n, cap,
+                       reinterpret_cast<const uint32_t*>(Wv.ht), reinterpret_cast<const uint32_t*>(Wv.hslot), Wv.vis,
+                       shadow ? 1 : 0, bad.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    uint32_t hbad[2] = {0u, 0u};
+    HIPCHK(hipMemcpyAsync(hbad, bad.p, sizeof(hbad), hipMemcpyDeviceToHost, c->stream));
     Counters hc;
     HIPCHK(hipMemcpyAsync(&hc, w.cnt.p, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
     KHPCHK(wait_stream(c, c->stream, "the ray queries"));
+    if (hbad[0] || hbad[1])
+        return fail(KHP_EDEVICE, "persistent query: " + std::to_string(hbad[0]) + " of " + std::to_string(n) +
+                                     " results never written, " + std::to_string(hbad[1]) +
+                                     " slots past the queue written");
     c->st.node_visits = shadow ? hc.sh_node_visits : hc.node_visits;
     c->st.prim_tests = shadow ? hc.sh_prim_tests : hc.prim_tests;
     c->st.stack_spills = hc.spills;
+    if (shadow) c->st.shadow_pruned_pops = hc.sh_pruned;
+    else c->st.extend_pruned_pops = hc.pruned;
     float kms = 0.0f;
     (void)hipEventElapsedTime(&kms, e0, e1);
     c->st.render_ms = kms;  // persistent query: traversal kernel time

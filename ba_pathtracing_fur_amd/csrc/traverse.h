@@ -86,6 +86,11 @@ __device__ __forceinline__ bool any_hit_x_nan(const DevScene& S, const Ray& r) {
 
 __device__ __forceinline__ bool ref_leaf(uint32_t r) { return (r & LEAF_BIT) != 0u; }
 
+// The wave's lanes with p set, as a wave-uniform value (the compiler keeps it and
+// what is computed from it in scalar registers; __ballot's int argument costs a
+// select and a compare on the vector side first).
+__device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
 struct PrivStack {
     uint32_t ref[STACK_MAX];
     float t0[STACK_MAX], t1[STACK_MAX];
@@ -192,6 +197,43 @@ struct LdsStack {
             b = f_from_bits((uint32_t)e.z);
             lo = sp;
         }
+    }
+    // Straight-line forms for the production step (stack_step below): every
+    // lane of the wave runs them, a lane takes part with on / want set.  The
+    // two rare paths -- a full ring spilling its oldest entry, a pop reaching
+    // spilled entries -- are regions the whole wave skips when no lane needs them.
+    __device__ __forceinline__ void push_sel(bool on, uint32_t r, float a, float b) {
+        if (on && sp - lo == R) {  // skipped by the whole wave unless a lane's ring is full
+            uint32_t k = slot(lo);
+            *gcell(lo) = make_int4((int)lds[k], (int)lds[k + R * TRAV_BLOCK], (int)lds[k + 2 * R * TRAV_BLOCK], 0);
+            ++lo;
+            if (COUNT) ++spills;
+        }
+        if (on) {
+            uint32_t k = slot(sp);
+            lds[k] = r;
+            lds[k + R * TRAV_BLOCK] = bits_from_f(a);
+            lds[k + 2 * R * TRAV_BLOCK] = bits_from_f(b);
+        }
+        sp += on ? 1 : 0;
+    }
+    // Reads the top slot whether the lane pops or not (an empty stack reads a
+    // stale slot of its own column); only a lane with `want` takes the entry.
+    __device__ __forceinline__ void pop_sel(bool want, uint32_t& r, float& a, float& b) {
+        const int top = sp - 1;
+        const uint32_t k = slot(top);
+        r = lds[k];
+        a = f_from_bits(lds[k + R * TRAV_BLOCK]);
+        b = f_from_bits(lds[k + 2 * R * TRAV_BLOCK]);
+        asm volatile("" : "+v"(r), "+v"(a), "+v"(b));  // the LDS reads happen here
+        if (want && top < lo) {  // skipped by the whole wave unless a lane reaches spilled entries
+            int4 e = *gcell(top);
+            r = (uint32_t)e.x;
+            a = f_from_bits((uint32_t)e.y);
+            b = f_from_bits((uint32_t)e.z);
+            lo = top;
+        }
+        sp = want ? top : sp;
     }
 };
 
@@ -473,6 +515,53 @@ __device__ __forceinline__ void take_entry(const DevScene& S, uint32_t ref, floa
     if (STATS && leaf) st.nodes++;
 }
 
+// The end of one production step, as one straight-line sequence of selects
+// for every lane of the wave: the pop (when the lane asked for one and its
+// stack is not empty), the pop-time prune test against tlimit, and take_entry
+// for the entry the lane goes on with -- `have`: (eref, et0, et1) from the
+// slab pair, else the popped entry if it passed the prune test.  A lane that
+// is idle or stays in its leaf changes nothing.  occ: the ray is occluded
+// (any hit).  Returns true when the ray is finished (occluded, or a pop from
+// an empty stack); the lane is then M_IDLE.  Same entries, order, counts and
+// arithmetic as the branches this replaced (push / pop / take_entry above);
+// the LEAF_CNT_ESC lookup stays a region the wave skips.
+template <bool STATS, class Stack>
+__device__ __forceinline__ bool stack_step(const DevScene& S, Stack& stk, float tlimit, bool occ, bool need_pop,
+                                           bool have, uint32_t eref, float et0, float et1, uint32_t& mode, Cur& c,
+                                           LeafCur& lf, TravStats& st) {
+    need_pop = need_pop && !occ;
+    const bool empty = stk.empty();
+    const bool want = need_pop && !empty;
+    const bool fin = occ || (need_pop && empty);
+    uint32_t pr;
+    float p0, p1;
+    stk.pop_sel(want, pr, p0, p1);
+    const bool pruned = want && (p1 < 0.0f || p0 > tlimit);
+    if (STATS) st.pruned += pruned ? 1u : 0u;
+    const bool take = have || (want && !pruned);
+    eref = have ? eref : pr;
+    et0 = have ? et0 : p0;
+    et1 = have ? et1 : p1;
+    const bool leaf = take && ref_leaf(eref);
+    uint32_t cnt = (eref >> 24) & 0x7Fu;
+    if (leaf && cnt == LEAF_CNT_ESC) cnt = S.aux[eref & 0x00FFFFFFu].flags >> 8;  // rare: skipped by the whole wave
+    c.ref = take ? eref : c.ref;
+    c.t0 = take ? et0 : c.t0;
+    c.t1 = take ? et1 : c.t1;
+    mode = take ? (leaf ? M_LEAF : M_NODE) : mode;  // take, pruned and fin exclude one another
+    mode = pruned ? M_POP : mode;
+    mode = fin ? M_IDLE : mode;
+    lf.slot = leaf ? (eref & 0x00FFFFFFu) : lf.slot;
+    lf.left = take ? (leaf ? cnt : 0u) : lf.left;
+    lf.tmax = take ? et1 : lf.tmax;
+    lf.tl = take ? FLT_MAX_ : lf.tl;
+    lf.lu = take ? 0.0f : lf.lu;
+    lf.lv = take ? 0.0f : lf.lv;
+    lf.sl = take ? -1 : lf.sl;
+    if (STATS) st.nodes += leaf ? 1u : 0u;
+    return fin;
+}
+
 // Start a ray: root box pre-test (BVH::closestIntersection / isIntersection).
 // Returns false when the ray misses the root box (finished at once).
 template <bool STATS, class Stack>
@@ -533,10 +622,16 @@ __device__ __forceinline__ void leaf_reuse(bool in_leaf, uint32_t slot) {
 }
 #endif
 
-// One wave iteration of one lane (mode != M_IDLE).  KIND 1: any-hit with the
-// fixed limit tlimit = the ray's tMax; KIND 0: closest hit, tlimit = h.t;
-// KIND 2: the lane's any_rt decides (the path kernel).  Returns true when the
-// ray is finished; for an any-hit query, `occluded` tells the result.
+// One wave iteration of one lane.  KIND 1: any-hit with the fixed limit
+// tlimit = the ray's tMax; KIND 0: closest hit, tlimit = h.t; KIND 2: the
+// lane's any_rt decides (the path kernel).  Returns true when the ray is
+// finished, and the lane is then M_IDLE; an any-hit query (KIND != 0) that
+// found an occluder sets `occluded`, which is otherwise left as it is -- the
+// caller clears it when it starts the ray.  A lane with mode == M_IDLE may
+// run the step too: it fetches, pushes and pops nothing, keeps its state and
+// returns false, so k_extend and k_shadow call it from every lane.
+// Three divergent regions remain: the record fetch, the slab pair, the
+// candidate test; everything after them is stack_step's straight line.
 template <int KIND, bool STATS, class Stack>
 __device__ __forceinline__ bool iter2k(const DevScene& S, const TravRay& tr, Hit& h, float tmax_any, Stack& stk,
                                        uint32_t& mode, Cur& c, LeafCur& lf, TravStats& st, bool& occluded,
@@ -563,7 +658,8 @@ __device__ __forceinline__ bool iter2k(const DevScene& S, const TravRay& tr, Hit
         pin(q0); pin(q1); pin(q2); pin(q3);
     }
     bool need_pop = mode == M_POP;
-    bool have = false;  // a new entry (ref, t0, t1) for take_entry
+    bool occ = false;   // any hit: this candidate occludes the ray
+    bool have = false;  // a new entry (ref, t0, t1) for stack_step
     uint32_t eref = 0u;
     float et0 = 0.0f, et1 = 0.0f;
     bool push = false;
@@ -574,19 +670,13 @@ __device__ __forceinline__ bool iter2k(const DevScene& S, const TravRay& tr, Hit
         if (KIND == 2) {
             float t = 0.0f;
             const bool ok = candidate_rt(q0, q1, q2, q3, tr.r, ANY, ANY ? tmax_any : lf.tmax, t);
-            if (ok && ANY) {
-                occluded = true;
-                return true;
-            }
+            occ = ok && ANY;
             if (ok) {
                 lf.sl = (int32_t)lf.slot;
                 lf.tmax = t;
             }
         } else if (ANY) {
-            if (any_candidate(q0, q1, q2, q3, tr.r, tmax_any)) {
-                occluded = true;
-                return true;
-            }
+            occ = any_candidate(q0, q1, q2, q3, tr.r, tmax_any);
         } else {
             leaf_candidate_t(q0, q1, q2, q3, (int32_t)lf.slot, tr.r, lf.tmax, lf.sl);
         }
@@ -625,24 +715,9 @@ __device__ __forceinline__ bool iter2k(const DevScene& S, const TravRay& tr, Hit
         pt0 = nearl ? r0 : l0;
         pt1 = nearl ? r1 : l1;
     }
-    if (push) stk.push(pref, pt0, pt1);
-    if (need_pop) {
-        if (stk.empty()) {
-            mode = M_IDLE;
-            occluded = false;
-            return true;
-        }
-        stk.pop(eref, et0, et1);
-        const float tlimit = ANY ? tmax_any : h.t;
-        if (et1 < 0.0f || et0 > tlimit) {
-            if (STATS) st.pruned++;
-            mode = M_POP;
-        } else {
-            have = true;
-        }
-    }
-    if (have) take_entry<STATS>(S, eref, et0, et1, mode, c, lf, st);
-    return false;
+    stk.push_sel(push, pref, pt0, pt1);
+    if (KIND != 0) occluded = occluded || occ;
+    return stack_step<STATS>(S, stk, ANY ? tmax_any : h.t, occ, need_pop, have, eref, et0, et1, mode, c, lf, st);
 }
 
 template <bool ANY, bool STATS, class Stack>
@@ -740,6 +815,7 @@ __device__ __forceinline__ bool iterwk(const DevScene& S, const TravRay& tr, Hit
         pin(q4); pin(q5); pin(q6); pin(q7);
     }
     bool need_pop = mode == M_POP;
+    bool occ = false;
     bool have = false;
     uint32_t eref = 0u;
     float et0 = 0.0f, et1 = 0.0f;
@@ -751,19 +827,13 @@ __device__ __forceinline__ bool iterwk(const DevScene& S, const TravRay& tr, Hit
         if (KIND == 2) {
             float t = 0.0f;
             const bool ok = candidate_rt(q0, q1, q2, q3, tr.r, ANY, ANY ? tmax_any : lf.tmax, t);
-            if (ok && ANY) {
-                occluded = true;
-                return true;
-            }
+            occ = ok && ANY;
             if (ok) {
                 lf.sl = (int32_t)lf.slot;
                 lf.tmax = t;
             }
         } else if (ANY) {
-            if (any_candidate(q0, q1, q2, q3, tr.r, tmax_any)) {
-                occluded = true;
-                return true;
-            }
+            occ = any_candidate(q0, q1, q2, q3, tr.r, tmax_any);
         } else {
             leaf_candidate_t(q0, q1, q2, q3, (int32_t)lf.slot, tr.r, lf.tmax, lf.sl);
         }
@@ -837,24 +907,10 @@ __device__ __forceinline__ bool iterwk(const DevScene& S, const TravRay& tr, Hit
         p2t0 = gnl ? gr0 : gl0;
         p2t1 = gnl ? gr1 : gl1;
     }
-    if (push1) stk.push(p1ref, p1t0, p1t1);
-    if (push2) stk.push(p2ref, p2t0, p2t1);
-    if (need_pop) {
-        if (stk.empty()) {
-            mode = M_IDLE;
-            occluded = false;
-            return true;
-        }
-        stk.pop(eref, et0, et1);
-        if (et1 < 0.0f || et0 > (ANY ? tmax_any : h.t)) {
-            if (STATS) st.pruned++;
-            mode = M_POP;
-        } else {
-            have = true;
-        }
-    }
-    if (have) take_entry<STATS>(S, eref, et0, et1, mode, c, lf, st);
-    return false;
+    stk.push_sel(push1, p1ref, p1t0, p1t1);
+    stk.push_sel(push2, p2ref, p2t0, p2t1);
+    if (KIND != 0) occluded = occluded || occ;
+    return stack_step<STATS>(S, stk, ANY ? tmax_any : h.t, occ, need_pop, have, eref, et0, et1, mode, c, lf, st);
 }
 
 template <bool ANY, bool STATS, class Stack>

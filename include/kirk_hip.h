@@ -292,7 +292,9 @@ typedef struct {
                                     synchronous render for khp_debug_queue (-1: off, default)       */
     uint32_t trace_kernels;      /* khp_trace_closest / khp_trace_any run on 0: one-ray-per-thread
                                     kernels (default), 1: the instrumented persistent kernels (KIRK's
-                                    visit counts), 2: the production persistent kernels             */
+                                    visit counts), 2: the production persistent kernels.  With 1 or
+                                    2 a query fails with KHP_EDEVICE if a result of the batch was
+                                    never written or a slot past the batch was (test hook)          */
     uint32_t shade_order;        /* ABI 7: 0 (default): k_shade takes the hits in queue order; 1: hits are
                                     first grouped by shading class (no hit / BSDF kind), a counting
                                     sort per bounce -- KIRK's GLSL template only compacts its hits
