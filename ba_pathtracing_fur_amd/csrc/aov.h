@@ -183,20 +183,17 @@ __global__ __launch_bounds__(256) void k_aov_reduce(AovCols R, AovOut O, const u
 struct AovState {
     DevMem rec, obj, cnt, spill, pix, stage;
     std::vector<uint32_t> pix_host;
-    uint32_t pix_key[5] = {0, 0, 0, 0, 0};
+    TileKey pix_key;
     int grid[2] = {0, 0};   // k_aov_trace<false> / <true>: resident blocks
     std::vector<float> host_tmp;
 };
 
 static khp_status aov_pixels(khp_ctx* c, AovState& A, const khp_render_params* p) {
-    const uint32_t T = p->tile_size ? p->tile_size : 64;
-    const uint32_t nranks = p->tile_nranks > 1 ? p->tile_nranks : 1;
-    const uint32_t rank = nranks > 1 ? p->tile_rank : 0;
-    const uint32_t key[5] = {p->width, p->height, T, rank, nranks};
-    if (memcmp(key, A.pix_key, sizeof(key)) == 0 && A.pix.p) return KHP_OK;
-    owned_pixels(p->width, p->height, T, rank, nranks, A.pix_host);
+    const TileKey key = tile_key(*p);
+    if (key == A.pix_key && A.pix.p) return KHP_OK;
+    key.pixels(A.pix_host);
     HIPCHK(upload(A.pix, A.pix_host.data(), A.pix_host.size(), c->stream));
-    memcpy(A.pix_key, key, sizeof(key));
+    A.pix_key = key;
     return KHP_OK;
 }
 
@@ -210,8 +207,7 @@ extern "C" khp_status khp_render_aov(khp_ctx* c, const khp_render_params* p, con
     if (p->spp > AOV_MAX_SPP) return fail(KHP_EINVAL, "spp must be at most 2^24");
     if ((uint64_t)p->width * p->height == 0) return fail(KHP_EINVAL, "width * height must be > 0");
     if ((uint64_t)p->width * p->height >= (1ull << 31)) return fail(KHP_EINVAL, "image too large");
-    const uint32_t T = p->tile_size ? p->tile_size : 64;
-    if (T % 8 != 0) return fail(KHP_EINVAL, "tile_size must be a multiple of 8");
+    if (tile_key(*p).tile % 8 != 0) return fail(KHP_EINVAL, "tile_size must be a multiple of 8");
     if (p->tile_nranks > 1 && p->tile_rank >= p->tile_nranks) return fail(KHP_EINVAL, "tile_rank >= tile_nranks");
     if (!c) return fail(KHP_EINVAL, "ctx is null");
     if (!c->scene_set) return fail(KHP_ENOTREADY, "khp_set_scene first");

@@ -1371,6 +1371,30 @@ __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_s
     }
 }
 
+// BSDF kind sets k_shade and k_path are instantiated for: every kind, or the fur scenes'
+// (Lambert reflection + Marschner hair: configs 1-3 and the metric row), where
+// the other kinds' code and registers are compiled out.
+constexpr uint32_t KINDS_ALL = (1u << KHP_BSDF_COUNT) - 1u;
+constexpr uint32_t KINDS_FUR = (1u << KHP_BSDF_LAMBERTIAN_REFLECTION) | (1u << KHP_BSDF_MARSCHNER_HAIR);
+// Host-side launch of the k_shade instance for (textured, light-path variant, fur-only scene, TT / TRT lobes);
+// grid_bd is the light-path instances' grid.  The lobe instances (never with the light-path variant) name their
+// kinds with KINDS_ALL; the others that keep every kind take k_shade's defaulted KINDS, a different instance.
+static void launch_shade(bool tex, bool bd, bool fur, bool lobes, int grid, int grid_bd, hipStream_t s,
+                         const DevScene& S, const Wave& W, int cur, uint32_t bounce) {
+    constexpr uint32_t DEFAULTED = 0xFFFFFFFFu;
+#define KHP_SHADE(TEX, BD, K) \
+    hipLaunchKernelGGL((k_shade<TEX, BD, K>), dim3(BD ? grid_bd : grid), dim3(shade_block<TEX, BD>()), 0, s, S, W, cur, bounce)
+    if (lobes && tex) KHP_SHADE(true, false, KINDS_ALL | KINDS_LOBES);   // TT / TRT compiled in
+    else if (lobes && fur) KHP_SHADE(false, false, KINDS_FUR | KINDS_LOBES);
+    else if (lobes) KHP_SHADE(false, false, KINDS_ALL | KINDS_LOBES);
+    else if (tex && bd) KHP_SHADE(true, true, DEFAULTED);
+    else if (tex) KHP_SHADE(true, false, DEFAULTED);
+    else if (bd) KHP_SHADE(false, true, DEFAULTED);
+    else if (fur) KHP_SHADE(false, false, KINDS_FUR);   // fur scenes: the other BSDF kinds compiled out
+    else KHP_SHADE(false, false, DEFAULTED);
+#undef KHP_SHADE
+}
+
 // ---- shadow: BVH::isIntersection (k_shadow), then the light occlusion loop and
 //      the deferred colour add (k_shadow_finish, SimpleShader.h:131-148) ---------------
 // k_shadow_finish: one shadow record per lane, streaming; kept out of the
@@ -2227,11 +2251,6 @@ __global__ __launch_bounds__(TRAV_BLOCK, PATH_WAVES) void k_path(DevScene S, Wav
 }
 
 constexpr size_t PATH_LDS = PATH_LDS_BYTES;
-// BSDF kind sets k_path is instantiated for: every kind, or the fur scenes'
-// (Lambert reflection + Marschner hair: configs 1-3 and the metric row), where
-// the other kinds' code and registers are compiled out.
-constexpr uint32_t KINDS_ALL = (1u << KHP_BSDF_COUNT) - 1u;
-constexpr uint32_t KINDS_FUR = (1u << KHP_BSDF_LAMBERTIAN_REFLECTION) | (1u << KHP_BSDF_MARSCHNER_HAIR);
 template <bool TEX, bool WIDE, uint32_t K>
 static void launch_path_k(int grid, hipStream_t s, const DevScene& S, const Wave& W, SpillArea sp, const PathLanes& L,
                           const Ahead& A, bool qs) {
@@ -2245,29 +2264,16 @@ static void launch_path_k(int grid, hipStream_t s, const DevScene& S, const Wave
 // lobes: the instances with Marschner's TT / TRT paths compiled in (khp_set_hair_lobes)
 static void launch_path(bool tex, bool wide, bool fur, bool lobes, int grid, hipStream_t s, const DevScene& S,
                         const Wave& W, SpillArea sp, const PathLanes& L, const Ahead& A, bool qs = false) {
-    if (lobes) {
-        if (tex) {
-            if (wide) launch_path_k<true, true, KINDS_ALL | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
-            else launch_path_k<true, false, KINDS_ALL | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
-        } else if (fur) {
-            if (wide) launch_path_k<false, true, KINDS_FUR | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
-            else launch_path_k<false, false, KINDS_FUR | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
-        } else {
-            if (wide) launch_path_k<false, true, KINDS_ALL | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
-            else launch_path_k<false, false, KINDS_ALL | KINDS_LOBES>(grid, s, S, W, sp, L, A, qs);
-        }
-        return;
-    }
-    if (tex) {
-        if (wide) launch_path_k<true, true, KINDS_ALL>(grid, s, S, W, sp, L, A, qs);
-        else launch_path_k<true, false, KINDS_ALL>(grid, s, S, W, sp, L, A, qs);
-    } else if (fur) {
-        if (wide) launch_path_k<false, true, KINDS_FUR>(grid, s, S, W, sp, L, A, qs);
-        else launch_path_k<false, false, KINDS_FUR>(grid, s, S, W, sp, L, A, qs);
-    } else {
-        if (wide) launch_path_k<false, true, KINDS_ALL>(grid, s, S, W, sp, L, A, qs);
-        else launch_path_k<false, false, KINDS_ALL>(grid, s, S, W, sp, L, A, qs);
-    }
+#define KHP_PATH(TEX, K)                                                    \
+    (wide ? launch_path_k<TEX, true, K>(grid, s, S, W, sp, L, A, qs)        \
+          : launch_path_k<TEX, false, K>(grid, s, S, W, sp, L, A, qs))
+    if (lobes && tex) KHP_PATH(true, KINDS_ALL | KINDS_LOBES);   // the ladder of launch_shade
+    else if (lobes && fur) KHP_PATH(false, KINDS_FUR | KINDS_LOBES);
+    else if (lobes) KHP_PATH(false, KINDS_ALL | KINDS_LOBES);
+    else if (tex) KHP_PATH(true, KINDS_ALL);
+    else if (fur) KHP_PATH(false, KINDS_FUR);
+    else KHP_PATH(false, KINDS_ALL);
+#undef KHP_PATH
 }
 
 // ---- accumulate: PathTracer::drawTexture running mean (CPU_PathTracer.cpp:61-90) -------
@@ -2609,7 +2615,6 @@ __global__ void k_unpack(float* fb, const uint32_t* pix, uint32_t P, const float
 //  host side
 // ============================================================================
 
-
 #define HIPCHK(expr)                                                                                     \
     do {                                                                                                 \
         hipError_t e_ = (expr);                                                                          \
@@ -2622,8 +2627,10 @@ __global__ void k_unpack(float* fb, const uint32_t* pix, uint32_t P, const float
         if (s_ != KHP_OK) return s_; \
     } while (0)
 
+// What a timed launch counts as in khp_stats (timed, harvest).
+enum TimedKind { T_EXTEND, T_SHADE, T_SHADOW /* any hit */, T_OTHER, T_SHADOW_FINISH };
 struct TimedLaunch {
-    int kind;  // 0 extend, 1 shade, 2 shadow (any hit), 3 other, 4 shadow finish
+    TimedKind kind;
     int bounce;
     hipEvent_t a, b;
 };
@@ -2693,12 +2700,22 @@ static hipEvent_t slot_event(std::vector<hipEvent_t>& pool, size_t& next, bool n
     }
     return pool[next++];
 }
+// What a render's owned-pixel list depends on: the image, the tile size (64 by
+// default) and the rank's place among those that share the image (alone: 0 of 1).
+struct TileKey {
+    uint32_t W = 0, H = 0, tile = 0, rank = 0, nranks = 0;
+    bool operator==(const TileKey& o) const { return memcmp(this, &o, sizeof(TileKey)) == 0; }   // five words, no padding
+    void pixels(std::vector<uint32_t>& out) const { owned_pixels(W, H, tile, rank, nranks, out); }
+};
+static TileKey tile_key(const khp_render_params& p) {
+    const uint32_t nranks = p.tile_nranks > 1 ? p.tile_nranks : 1;
+    return TileKey{p.width, p.height, p.tile_size ? p.tile_size : 64, nranks > 1 ? p.tile_rank : 0u, nranks};
+}
 
 struct khp_ctx {
     int device = 0;
     uint32_t flags = 0;
     hipStream_t stream = nullptr;
-    std::vector<hipEvent_t> sync_pool;  // ordering events (no timing)
     int n_cu = 256;
     HostScene hs;
     bool scene_set = false, built = false;
@@ -2737,11 +2754,10 @@ struct khp_ctx {
     std::vector<float> dump_sh;  // prm.dump_bounce: that bounce's shadow rays, o.xyz d.xyz t_max each
     uint32_t fbW = 0, fbH = 0;
     std::vector<uint32_t> pix_host;
-    uint32_t pix_key[5] = {0, 0, 0, 0, 0};
+    TileKey pix_key;
     // timing
     std::vector<hipEvent_t> ev_pool;
     size_t ev_next = 0;
-    std::vector<TimedLaunch> launches;
     int grid_ext = 0, grid_ext_w = 0, grid_ext_cam = 0, grid_sh = 0, grid_shade = 0;  // k_extend: 64-B, wide, bounce 0
     int grid_fin = 0;    // k_shadow_finish
     int grid_shade_bd = 0;   // k_shade with the light-path variant (512-thread blocks)
@@ -2796,12 +2812,15 @@ struct khp_ctx {
     // render-ahead (khp_ctx_params.render_ahead, ABI 13; k_path's Ahead): the work a
     // synchronous path-kernel call did for the next call of its progressive series
     uint64_t gen = 1;   // bumped by every change of the scene, camera or parameters
+    struct NextCall {   // the call expected next in a progressive series (series_successor), noted under generation gen
+        bool valid = false;
+        khp_render_params p{};
+        uint64_t gen = 0;
+    };
     struct AheadSet {
         DevMem st, ck, park;         // AheadState; per ring slot: colour column, park list
-        bool valid = false;          // the ring's slot `own` holds the set of the call `next`
+        NextCall next;               // valid: the ring's slot `own` holds the set of that call
         uint32_t own = 0, nsets = 0, park_cap = 0;
-        khp_render_params next{};
-        uint64_t gen = 0;
         size_t npaths = 0;
         uint32_t* hst = nullptr;     // pinned: AheadState::report of the current call
         bool counted = false;        // hst was filled by the current call
@@ -2811,20 +2830,28 @@ struct khp_ctx {
     // the same fused batch; their colours stay in ps[0]'s colour column until those
     // calls accumulate them (wave_ahead_hit).  Any other use of ps[0] drops the batch.
     struct WaveAhead {
-        bool valid = false;
-        khp_render_params next{};    // the call whose pass is the batch's next frame
-        uint64_t gen = 0;
+        NextCall next;               // the call whose pass is the batch's next frame
         Wave Wv{};                   // the batch's view: colour column, pixel list, frames' first samples
         uint32_t nf = 0, used = 0;   // frames in the batch, frames accumulated so far
     } wa;
-    struct {   // the last synchronous single-pass call, first_sample advanced by its spp
-        bool valid = false;
-        khp_render_params next{};
-        uint64_t gen = 0;
-    } series;
+    NextCall series;   // the last synchronous single-pass call, first_sample advanced by its spp
     std::shared_ptr<struct AovState> aov;   // khp_render_aov's own scratch (aov.h), made by its first call
 };
 constexpr size_t LG_SLOTS = 64;
+
+// Decisions read off the context or a call, each written here once: a fur scene (only KINDS_FUR's BSDF kinds);
+// the light-path variant runs, its records per path and bounce; the most frames per fused batch, batches in flight.
+static bool fur_only(const khp_ctx* c) { return (c->bsdf_kinds & ~KINDS_FUR) == 0u; }
+static bool light_paths_on(const khp_ctx* c) { return c->bd.enabled != 0 && c->S.n_lights > 0; }
+static uint32_t shadow_records_per_path(const khp_ctx* c) { return light_paths_on(c) ? c->bd.vertices : 1u; }
+static uint32_t fuse_limit(const khp_ctx* c) { return std::max(1u, std::min<uint32_t>(c->prm.fuse_frames, KHP_MAX_FUSE)); }
+static int frames_in_flight(const khp_ctx* c) {
+    return (int)std::max(1u, std::min<uint32_t>(c->prm.frames_in_flight, KHP_MAX_INFLIGHT));
+}
+static bool render_stats(const khp_ctx* c, const khp_render_params* p) {
+    return (c->flags & KHP_CTX_STATS) != 0 || (p->flags & KHP_RENDER_STATS) != 0;
+}
+static bool render_async(const khp_render_params* p) { return (p->flags & KHP_RENDER_ASYNC) != 0; }
 
 static khp_status drain(khp_ctx* c);
 static void comm_release(khp_ctx* c);
@@ -2964,16 +2991,6 @@ static hipEvent_t next_event(khp_ctx* c) {
         c->ev_pool.push_back(e);
     }
     return c->ev_pool[c->ev_next++];
-}
-
-// Ordering event k of this render (created once, reused across renders).
-static hipEvent_t sync_event(khp_ctx* c, size_t k) {
-    while (c->sync_pool.size() <= k) {
-        hipEvent_t e;
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-        c->sync_pool.push_back(e);
-    }
-    return c->sync_pool[k];
 }
 
 extern "C" int khp_abi_version(void) { return KHP_ABI_VERSION; }
@@ -3150,7 +3167,6 @@ extern "C" void khp_destroy(khp_ctx* c) {
         for (auto e : f.sync_pool) (void)hipEventDestroy(e);
     }
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    for (auto e : c->sync_pool) (void)hipEventDestroy(e);
     if (c->tm_hl) (void)hipHostFree(c->tm_hl);
     if (c->tm_hm) (void)hipHostFree(c->tm_hm);
     if (c->ra.hst) (void)hipHostFree(c->ra.hst);
@@ -3498,7 +3514,7 @@ extern "C" khp_status khp_build_accel(khp_ctx* c) {
         c->bsdf_kinds |= (m.bsdf >= 0 && m.bsdf < KHP_BSDF_COUNT) ? (1u << m.bsdf) : KINDS_ALL;
     nb = 0;
     if (S.textured) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_shade<true, false>), shade_block<true, false>(), 0));
-    else if ((c->bsdf_kinds & ~KINDS_FUR) == 0u)
+    else if (fur_only(c))
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_shade<false, false, KINDS_FUR>), shade_block<false, false>(), 0));
     else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_shade<false, false>), shade_block<false, false>(), 0));
     c->grid_shade = std::max(1, nb) * c->n_cu;
@@ -3592,14 +3608,11 @@ static Wave wave_view(const khp_ctx* c, PathSet& w) {
 }
 
 static khp_status prepare_pixels(khp_ctx* c, const khp_render_params* p) {
-    uint32_t T = p->tile_size ? p->tile_size : 64;
-    uint32_t nranks = p->tile_nranks > 1 ? p->tile_nranks : 1;
-    uint32_t rank = nranks > 1 ? p->tile_rank : 0;
-    uint32_t key[5] = {p->width, p->height, T, rank, nranks};
-    if (memcmp(key, c->pix_key, sizeof(key)) == 0 && c->pix.p) return KHP_OK;
-    owned_pixels(p->width, p->height, T, rank, nranks, c->pix_host);
+    const TileKey key = tile_key(*p);
+    if (key == c->pix_key && c->pix.p) return KHP_OK;
+    key.pixels(c->pix_host);
     HIPCHK(upload(c->pix, c->pix_host.data(), c->pix_host.size(), c->stream));
-    memcpy(c->pix_key, key, sizeof(key));
+    c->pix_key = key;
     return KHP_OK;
 }
 
@@ -3626,7 +3639,7 @@ static size_t chunk_paths(khp_ctx* c) {
 }
 
 // The most paths one fused chunk may hold: the cap, or with automatic chunking
-// 5/4 of it (enqueue_frames cuts a batch into one chunk fewer when the chunks
+// 5/4 of it (plan_batch cuts a batch into one chunk fewer when the chunks
 // then stay within this; flush() groups gathered frames by the same limit).
 static size_t chunk_most(khp_ctx* c) {
     const size_t cap = chunk_paths(c);
@@ -3638,13 +3651,12 @@ static khp_status check_params(khp_ctx* c, const khp_render_params* p) {
     if (!c->built) return fail(KHP_ENOTREADY, "khp_build_accel first");
     if (p->width == 0 || p->height == 0 || p->depth == 0) return fail(KHP_EINVAL, "width/height/depth must be > 0");
     if ((uint64_t)p->width * p->height >= (1ull << 31)) return fail(KHP_EINVAL, "image too large");
-    uint32_t T = p->tile_size ? p->tile_size : 64;
-    if (T % 8 != 0) return fail(KHP_EINVAL, "tile_size must be a multiple of 8");
+    if (tile_key(*p).tile % 8 != 0) return fail(KHP_EINVAL, "tile_size must be a multiple of 8");
     if (p->tile_nranks > 1 && p->tile_rank >= p->tile_nranks) return fail(KHP_EINVAL, "tile_rank >= tile_nranks");
     return KHP_OK;
 }
 
-static void timed(khp_ctx* c, FrameSlot& f, int kind, bool begin, hipStream_t st) {
+static void timed(khp_ctx* c, FrameSlot& f, TimedKind kind, bool begin, hipStream_t st) {
     hipEvent_t e = slot_event(f.ev_pool, f.ev_next, false);
     if (!e) return;
     (void)hipEventRecord(e, st);
@@ -3710,27 +3722,26 @@ static khp_status harvest(khp_ctx* c, int slot) {
     for (auto& l : f.launches) {
         float t = 0.0f;
         if (l.b && hipEventElapsedTime(&t, l.a, l.b) == hipSuccess) {
-            if (l.kind == 0) {
+            if (l.kind == T_EXTEND) {
                 c->st.extend_ms += t;
                 c->st.extend_launches++;
                 float t0 = 0.0f, t1 = 0.0f;
                 if (hipEventElapsedTime(&t0, c->report_ref, l.a) == hipSuccess &&
                     hipEventElapsedTime(&t1, c->report_ref, l.b) == hipSuccess)
                     c->ext_iv.push_back({t0, t1});
-            }
-            else if (l.kind == 1) c->st.shade_ms += t;
-            else if (l.kind == 2) {
+            } else if (l.kind == T_SHADE) c->st.shade_ms += t;
+            else if (l.kind == T_SHADOW) {
                 c->st.shadow_ms += t;
                 c->st.shadow_launches++;
-            } else if (l.kind == 4) {
+            } else if (l.kind == T_SHADOW_FINISH) {
                 c->st.shadow_ms += t;
                 c->st.shadow_finish_ms += t;
             } else {
                 c->st.other_ms += t;
             }
             if (l.bounce >= 0 && l.bounce < KHP_MAX_BOUNCE_STATS) {
-                if (l.kind == 0) c->st.bounce_extend_ms[l.bounce] += t;
-                if (l.kind == 2 || l.kind == 4) c->st.bounce_shadow_ms[l.bounce] += t;
+                if (l.kind == T_EXTEND) c->st.bounce_extend_ms[l.bounce] += t;
+                if (l.kind == T_SHADOW || l.kind == T_SHADOW_FINISH) c->st.bounce_shadow_ms[l.bounce] += t;
             }
         }
     }
@@ -3779,12 +3790,8 @@ static khp_status harvest(khp_ctx* c, int slot) {
 // other than through an asynchronous render calls this first.
 static khp_status flush(khp_ctx* c);
 static khp_status drain(khp_ctx* c) {
-    khp_status fr = flush(c);
-    if (fr != KHP_OK) return fr;
-    for (int s = 0; s < KHP_MAX_INFLIGHT; ++s) {
-        khp_status r = harvest(c, s);
-        if (r != KHP_OK) return r;
-    }
+    KHPCHK(flush(c));
+    for (int s = 0; s < KHP_MAX_INFLIGHT; ++s) KHPCHK(harvest(c, s));
     if (c->stream) KHPCHK(wait_stream(c, c->stream, "the context stream"));
     return KHP_OK;
 }
@@ -3801,9 +3808,6 @@ extern "C" khp_status khp_sync(khp_ctx* c) {
     return deliver_snapshots(c, UINT64_MAX, true);
 }
 
-// Enqueue one frame, or a fused batch of asynchronous frames (ops: their
-// render operations, which differ only in first_sample, and the framebuffer
-// gathers between them, in call order; p = the first render's parameters).
 static khp_status gather_now(khp_ctx* c, const khp_render_params* p, int root);
 static khp_status snapshot_now(khp_ctx* c, uint64_t id);
 // A non-render operation of a fused batch, in call order.
@@ -3822,13 +3826,26 @@ static bool ahead_key_equal(const khp_render_params& a, const khp_render_params&
            a.first_sample == b.first_sample && a.tile_size == b.tile_size && a.tile_rank == b.tile_rank &&
            a.tile_nranks == b.tile_nranks;
 }
+// This call's successor in its progressive series: the same call, first_sample advanced by its spp.
+static khp_render_params series_successor(const khp_render_params& p) {
+    khp_render_params next = p;
+    next.first_sample = p.first_sample + p.spp;
+    return next;
+}
+// Work done for p's successor (khp_ctx::ra, wa, series) is noted under the context's generation;
+// is_expected tells whether the call p is the one it was done for.
+static void expect_successor(khp_ctx::NextCall& n, const khp_ctx* c, const khp_render_params& p) {
+    n = khp_ctx::NextCall{true, series_successor(p), c->gen};
+}
+static bool is_expected(const khp_ctx::NextCall& n, const khp_ctx* c, const khp_render_params& p) {
+    return n.valid && n.gen == c->gen && ahead_key_equal(n.p, p);
+}
 static khp_status ahead_prepare(khp_ctx* c, const khp_render_params* p, size_t npaths, hipStream_t s, Ahead& A,
                                 float4** ck_own) {
     khp_ctx::AheadSet& ra = c->ra;
     const uint32_t nsets = std::min<uint32_t>(c->prm.render_ahead, RA_MAX_SETS - 1) + 1;
-    const bool match = ra.valid && ra.gen == c->gen && ra.npaths == npaths && ra.nsets == nsets &&
-                       ahead_key_equal(ra.next, *p);
-    ra.valid = false;
+    const bool match = is_expected(ra.next, c, *p) && ra.npaths == npaths && ra.nsets == nsets;
+    ra.next.valid = false;
     // a lane parks at most one path per launch, and a set is parked by the nsets - 1
     // launches before the one it belongs to
     const size_t lanes = (size_t)c->grid_path * TRAV_BLOCK;
@@ -3865,12 +3882,8 @@ static khp_status ahead_prepare(khp_ctx* c, const khp_render_params* p, size_t n
     return KHP_OK;
 }
 static void ahead_commit(khp_ctx* c, const khp_render_params* p, size_t npaths) {
-    khp_ctx::AheadSet& ra = c->ra;
-    ra.valid = true;
-    ra.next = *p;
-    ra.next.first_sample = p->first_sample + p->spp;
-    ra.gen = c->gen;
-    ra.npaths = npaths;
+    expect_successor(c->ra.next, c, *p);
+    c->ra.npaths = npaths;
 }
 
 // Render-ahead through fusion: the synchronous call p is the next frame of the
@@ -3889,8 +3902,8 @@ static khp_status wave_ahead_hit(khp_ctx* c, const khp_render_params* p, float* 
     HIPCHK(hipGetLastError());
     (void)hipEventRecord(e1, c->stream);
     ++wa.used;
-    wa.next.first_sample = p->first_sample + p->spp;
-    if (wa.used >= wa.nf) wa.valid = false;
+    wa.next.p = series_successor(*p);
+    if (wa.used >= wa.nf) wa.next.valid = false;
     if (out_rgb && !(p->flags & KHP_RENDER_NO_READBACK)) {
         hipMemcpyKind kind = (p->flags & KHP_RENDER_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
         HIPCHK(hipMemcpyAsync(out_rgb, c->fb.p, (size_t)p->width * p->height * 3 * sizeof(float), kind, c->stream));
@@ -3903,118 +3916,91 @@ static khp_status wave_ahead_hit(khp_ctx* c, const khp_render_params* p, float* 
     c->st.frames = 1;
     c->st.ahead_finished = (uint64_t)P * p->spp;
     c->report_open = false;
-    c->series.valid = true;
-    c->series.next = *p;
-    c->series.next.first_sample = p->first_sample + p->spp;
-    c->series.gen = c->gen;
+    expect_successor(c->series, c, *p);
     return KHP_OK;
 }
 
-static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* out_rgb,
-                                 const std::vector<PendingOp>* ops) {
-    khp_status s;
-    const bool stats = (c->flags & KHP_CTX_STATS) != 0 || (p->flags & KHP_RENDER_STATS) != 0;
-    const bool async = (p->flags & KHP_RENDER_ASYNC) != 0;
-    // fused frames: their first samples, in call order
-    std::vector<uint32_t> fs0;
-    if (ops) {
-        for (const PendingOp& o : *ops)
-            if (o.kind == PendingOp::RENDER) fs0.push_back(o.p.first_sample);
-    } else {
-        fs0.push_back(p->first_sample);
-    }
-    uint32_t nf = (uint32_t)fs0.size();
-    const size_t npix = (size_t)p->width * p->height;
-    uint32_t T = p->tile_size ? p->tile_size : 64;
-    uint32_t nranks = p->tile_nranks > 1 ? p->tile_nranks : 1;
-    uint32_t pkey[5] = {p->width, p->height, T, nranks > 1 ? p->tile_rank : 0u, nranks};
-    const bool geometry_change = c->fbW != p->width || c->fbH != p->height || !c->fb.p ||
-                                 memcmp(pkey, c->pix_key, sizeof(pkey)) != 0 || !c->pix.p;
-    if (!async || geometry_change) {  // a synchronous render (or new buffers) first completes the in-flight frames
-        s = drain(c);
-        if (s != KHP_OK) return s;
-        // An asynchronous frame on new buffers keeps accumulating into the
-        // report opened since the last khp_sync; only a synchronous render
-        // starts a fresh one.
-        if (!async) c->report_open = false;
-    }
-    if (!async) report_begin(c);
-    else if (!c->report_open) report_begin(c);
-    // render-ahead through fusion (c->wa): a synchronous single pass that an earlier
-    // call already rendered only accumulates; every other render drops the batch
-    const bool sync1 = !async && !ops && nf == 1;
-    const bool continues = sync1 && c->series.valid && c->series.gen == c->gen && ahead_key_equal(c->series.next, *p);
-    c->series.valid = false;
-    if (sync1 && !stats && c->wa.valid && c->wa.gen == c->gen && ahead_key_equal(c->wa.next, *p) && c->fb.p &&
-        c->fbW == p->width && c->fbH == p->height)
-        return wave_ahead_hit(c, p, out_rgb);
-    c->wa.valid = false;
-    if (c->fbW != p->width || c->fbH != p->height || !c->fb.p) {
-        HIPCHK(c->fb.ensure(npix * 3 * sizeof(float)));
-        HIPCHK(hipMemsetAsync(c->fb.p, 0, npix * 3 * sizeof(float), c->stream));
-        HIPCHK(c->pixheavy.ensure(npix));
-        HIPCHK(hipMemsetAsync(c->pixheavy.p, 0, npix, c->stream));
-        c->fbW = p->width;
-        c->fbH = p->height;
-    }
-    s = prepare_pixels(c, p);
-    if (s != KHP_OK) return s;
-    if (geometry_change) KHPCHK(wait_stream(c, c->stream, "the framebuffer setup"));
-    const uint32_t P_all = (uint32_t)c->pix_host.size();
-    // Batches in flight: an asynchronous render takes the next frame slot (its
-    // own path set and streams) and returns once enqueued; up to
-    // prm.frames_in_flight batches then run at the same time, each persistent
-    // launch taking 1/F of the resident grid.  The framebuffer is written in
-    // render order: each accumulate waits for the previous framebuffer
-    // operation (accumulate or gather).
-    const int F = (int)std::max<uint32_t>(1, std::min<uint32_t>(c->prm.frames_in_flight, KHP_MAX_INFLIGHT));
-    const int slot = async ? (int)(c->frame_no % (uint64_t)F) : 0;
-    c->frame_no += async ? 1 : 0;
-    s = harvest(c, slot);  // the slot's previous batch (async series)
-    if (s != KHP_OK) return s;
-    FrameSlot& f = c->fs[slot];
-    f.ev_next = 0;
-    f.sync_next = 0;
-    f.launches.clear();
-    f.snaps.clear();
-    const int G = async ? F : 1;
-    const int grid_ext = std::max(1, c->grid_ext / G), grid_sh = std::max(1, c->grid_sh / G);
-    const int grid_sh_w = std::max(1, c->grid_sh_w / G);
-    const int grid_ext_w = std::max(1, c->grid_ext_w / G), grid_ext_cam = std::max(1, c->grid_ext_cam / G);
+// ---- the batch driver: enqueue_frames = open_batch, plan_batch, reserve_batch, the fork,
+//      enqueue_chunk per chunk (enqueue_bounce per bounce, enqueue_accumulate), the join ----
+// What open_batch found before anything is planned.
+struct BatchOpening {
+    bool sync1 = false, continues = false;   // a synchronous single pass; one that follows the previous in its series
+    bool geometry_change = false;  // new framebuffer or pixel list: the batch forks from the context stream
+    bool served = false;           // the pass was rendered ahead and is accumulated (wave_ahead_hit): nothing to enqueue
+    int slot = 0;                  // the frame slot (its path set and streams)
+};
+// Every decision enqueue_frames makes before it enqueues anything (plan_batch); the stages read them here.
+struct BatchPlan {
+    bool stats, async, sync1, continues;
+    std::vector<uint32_t> fs0;   // fused frames: their first samples, in call order
+    uint32_t nf, wa_frames;      // fs0.size(); of them this call's pass + those rendered ahead through fusion (1: off)
+    bool only_renders;           // no gather or snapshot among the batch's operations
+    uint32_t P_all, P_chunk, S_chunk;   // owned pixels; pixels and samples per chunk
+    size_t call_paths;           // P_all x spp x nf
+    bool bdm;                    // the light-path variant, with sh_per_path connection records per path
+    uint32_t sh_per_path;
+    int dump_b;                  // the bounce whose queues are dumped (-1: none)
+    bool use_path, path_wide;    // the path kernel; on the two-level records
+    uint32_t hyb_from, rs_from;  // k_path takes over at this bounce (hybrid batches); ray sorting from this one (0: off)
+    bool hyb_wide, ahead;        // ahead: render-ahead in the path kernel
+    bool lobes_on, fur_only;     // khp_set_hair_lobes: the KINDS_LOBES instances; the KINDS_FUR instances
+    bool overlap;                // the shadow stage on its own stream
+    int grid_ext, grid_ext_w, grid_ext_cam, grid_sh, grid_sh_w, grid_path;   // this batch's share of the resident grids
+};
+
+// the path kernel (khp_ctx_params.path_kernel): automatic for synchronous renders of at
+// most PATH_AUTO_MAX paths.  At the metric row a synchronous call of s spp takes
+// 8.0 / 12.5 / 16.7 / 20.8 / 29.4 / 37.6 ms through it for s = 1 / 2 / 3 / 4 / 6 / 8
+// against 14.0 / 17.9 / 21.4 / 24.7 / 31.2 / 37.2 through the wavefront
+// (profiles/r04aa_sync_spp.json): the wavefront's better steady rate wins from ~7.5 spp
+constexpr size_t PATH_AUTO_MAX = (size_t)14 << 20;
+static bool routes_to_path_kernel(const khp_ctx* c, bool path_ok, bool async, size_t paths) {
+    return path_ok && (c->prm.path_kernel == 2 || (c->prm.path_kernel == 0 && !async && paths <= PATH_AUTO_MAX));
+}
+// Allocates nothing; hipMemGetInfo (chunk_paths, the light subpaths' share) is its only HIP call.
+static khp_status plan_batch(khp_ctx* c, const khp_render_params* p, const std::vector<PendingOp>* ops,
+                             const BatchOpening& o, BatchPlan& pl) {
+    pl.stats = render_stats(c, p);
+    pl.async = render_async(p);
+    pl.sync1 = o.sync1;
+    pl.continues = o.continues;
+    if (!ops) pl.fs0.push_back(p->first_sample);
+    else
+        for (const PendingOp& op : *ops)
+            if (op.kind == PendingOp::RENDER) pl.fs0.push_back(op.p.first_sample);
+    pl.only_renders = !ops || pl.fs0.size() == ops->size();
+    const uint32_t P_all = pl.P_all = (uint32_t)c->pix_host.size();
+    // each persistent launch of a batch in flight takes 1/F of the resident grid
+    const int G = pl.async ? frames_in_flight(c) : 1;
+    pl.grid_ext = std::max(1, c->grid_ext / G), pl.grid_sh = std::max(1, c->grid_sh / G);
+    pl.grid_sh_w = std::max(1, c->grid_sh_w / G);
+    pl.grid_ext_w = std::max(1, c->grid_ext_w / G), pl.grid_ext_cam = std::max(1, c->grid_ext_cam / G);
     // Chunks: the owned pixels x samples (x fused frames) are cut into chunks
     // of at most chunk_paths() paths, pixel-major; a fused chunk carries all
     // samples of all frames of its pixels.
     // light-path variant: up to `vertices` connection records per path and bounce,
     // so a chunk carries 1/vertices of the paths (the same shadow-record memory)
-    const bool bdm = c->bd.enabled != 0 && c->S.n_lights > 0;
-    const uint32_t sh_per_path = bdm ? c->bd.vertices : 1u;
+    const bool bdm = pl.bdm = light_paths_on(c);
+    const uint32_t sh_per_path = pl.sh_per_path = shadow_records_per_path(c);
     const size_t cap_paths = std::max<size_t>(4096 / sh_per_path, chunk_paths(c) / sh_per_path);
-    const int dump_b = (!async && !ops) ? c->prm.dump_bounce : -1;
-    // the path kernel (khp_ctx_params.path_kernel): automatic for synchronous renders of at
-    // most PATH_AUTO_MAX paths.  At the metric row a synchronous call of s spp takes
-    // 8.0 / 12.5 / 16.7 / 20.8 / 29.4 / 37.6 ms through it for s = 1 / 2 / 3 / 4 / 6 / 8
-    // against 14.0 / 17.9 / 21.4 / 24.7 / 31.2 / 37.2 through the wavefront
-    // (profiles/r04aa_sync_spp.json): the wavefront's better steady rate wins from ~7.5 spp
-    constexpr size_t PATH_AUTO_MAX = (size_t)14 << 20;
-    const bool path_ok = !stats && !bdm && c->prm.shade_order == 0 && dump_b < 0;
+    pl.dump_b = (!pl.async && !ops) ? c->prm.dump_bounce : -1;
+    const bool path_ok = !pl.stats && !bdm && c->prm.shade_order == 0 && pl.dump_b < 0;
     // render-ahead through fusion: a synchronous wavefront call that continues its series
     // (the previous synchronous call was its pass with first_sample - spp) renders itself and
     // the next render_ahead calls' passes as one fused batch of one chunk, accumulates its own
     // frame and leaves the others' colours for those calls (8-spp calls at the metric row:
     // a batch of 3 / 4 passes costs 28.6 / 27.5 ms per pass against 36.8 alone,
     // profiles/r06t_fuse_probe.jsonl)
-    uint32_t wa_frames = 1;
-    if (continues && c->prm.render_ahead != 0 && !stats && !bdm && dump_b < 0 && P_all > 0) {
+    pl.wa_frames = 1;
+    if (pl.continues && c->prm.render_ahead != 0 && !pl.stats && !bdm && pl.dump_b < 0 && P_all > 0) {
         const size_t one = (size_t)P_all * p->spp;
-        const bool wavefront = !(path_ok && (c->prm.path_kernel == 2 ||
-                                             (c->prm.path_kernel == 0 && one <= PATH_AUTO_MAX)));
-        const uint32_t F = 1u + std::min<uint32_t>(c->prm.render_ahead, RA_MAX_SETS - 1);
-        if (wavefront && one * F <= cap_paths && F <= KHP_MAX_FUSE) wa_frames = F;
+        const uint32_t passes = 1u + std::min<uint32_t>(c->prm.render_ahead, RA_MAX_SETS - 1);
+        if (!routes_to_path_kernel(c, path_ok, pl.async, one) && one * passes <= cap_paths && passes <= KHP_MAX_FUSE)
+            pl.wa_frames = passes;
     }
-    for (uint32_t q = 1; q < wa_frames; ++q) fs0.push_back(p->first_sample + q * p->spp);
-    nf = (uint32_t)fs0.size();
-    f.nf = nf;
-    uint32_t P_chunk, S_chunk;
+    for (uint32_t q = 1; q < pl.wa_frames; ++q) pl.fs0.push_back(p->first_sample + q * p->spp);
+    const uint32_t nf = pl.nf = (uint32_t)pl.fs0.size();
+    uint32_t &P_chunk = pl.P_chunk, &S_chunk = pl.S_chunk;
     if (nf > 1) {
         P_chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(std::max<uint32_t>(1, P_all),
                                                                  cap_paths / ((size_t)p->spp * nf)));
@@ -4041,37 +4027,80 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
         P_chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(P_all, cap_paths));
         S_chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(p->spp, cap_paths / P_chunk));
     }
-    if (ops && (P_chunk < P_all || S_chunk < p->spp)) {
-        for (const PendingOp& o : *ops)  // flush() groups gathered frames so that each group is one chunk
-            if (o.kind != PendingOp::RENDER)
-                return fail(KHP_EINVAL, "internal: a fused batch with gathers or snapshots spans more than one chunk");
-    }
+    // flush() groups gathered frames so that each group is one chunk
+    if (!pl.only_renders && (P_chunk < P_all || S_chunk < p->spp))
+        return fail(KHP_EINVAL, "internal: a fused batch with gathers or snapshots spans more than one chunk");
     if (bdm && nf == 1) {  // the light subpaths of a chunk's sample slots take at most a quarter of the free HBM
         size_t free_b = 0, total_b = 0;
         const size_t per_slot = (size_t)c->bd.light_paths * c->S.n_lights * c->bd.vertices * 48;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && per_slot)
             S_chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(S_chunk, free_b / 4 / per_slot));
     }
+    pl.call_paths = (size_t)P_all * p->spp * nf;
+    pl.use_path = routes_to_path_kernel(c, path_ok, pl.async, pl.call_paths);
+    pl.path_wide = pl.use_path && c->S.wide != nullptr && c->prm.wide_from == 0;
+    // hybrid batches (khp_ctx_params.path_from): a wavefront render hands the paths still
+    // alive at bounce path_from to one k_path launch, which carries them through the
+    // remaining bounces without a barrier per bounce (not with the light-path variant,
+    // hit sorting, instrumented renders or queue dumps)
+    pl.hyb_from = (path_ok && !pl.use_path && c->prm.path_from > 0 && c->prm.path_from < p->depth) ? c->prm.path_from : 0u;
+    pl.hyb_wide = pl.hyb_from > 0 && c->S.wide != nullptr && pl.hyb_from >= c->prm.wide_from;
+    pl.grid_path = std::max(1, ((pl.path_wide || pl.hyb_wide) ? c->grid_path_w : c->grid_path) / G);
+    pl.lobes_on = c->S.hair_lobes != HAIR_LOBE_R;
+    pl.fur_only = fur_only(c);
+    // Two streams: A runs generate / extend / shade / accumulate, B runs the
+    // shadow stage (k_shadow + k_shadow_finish) of bounce b while A already
+    // traverses bounce b+1, so each persistent kernel's tail fills with the
+    // other's blocks.  Ordering: B(b) after shade(b) on A; shade(b+1) after
+    // B(b) (both update the path colour C in bounce order); the shadow queue
+    // of bounce b+2 reuses parity b's buffers only after shade(b+1), which
+    // already waited for B(b).  Instrumented renders run everything on the
+    // context stream so the per-bounce snapshots are exact.
+    pl.overlap = !pl.stats && !c->prm.serial_stages;
+    // render-ahead (khp_ctx_params.render_ahead): synchronous path-kernel calls of one chunk
+    pl.ahead = pl.use_path && !pl.async && !ops && nf == 1 && c->prm.render_ahead != 0 && P_all > 0 &&
+               P_chunk >= P_all && S_chunk >= p->spp && pl.call_paths <= (size_t)PID_MASK + 1;
+    // ray sorting from bounce rs_from (0: off); not with hit sorting, the light-path
+    // variant or queue dumps, which read the queues in their own order.  Automatic
+    // (ray_sort_from 0): from bounce 2 when the node records exceed RS_AUTO_BYTES --
+    // a cache-resident tree has no misses to save (config 2: -3.6%, config 1: -17%)
+    const uint32_t rs_param = c->prm.ray_sort_from != 0 ? c->prm.ray_sort_from
+                              : (uint64_t)c->n_dnodes * sizeof(DevNode) >= RS_AUTO_BYTES ? 2u : 0u;
+    pl.rs_from = (c->prm.shade_order == 0 && !bdm && pl.dump_b < 0) ? rs_param : 0u;
+    return KHP_OK;
+}
+
+// Where one batch is enqueued: its frame slot, path set, stream pair and device views.
+// enqueue_frames and reserve_batch fill it; enqueue_chunk points Wv at its chunk.
+struct BatchTarget {
+    FrameSlot& f;
+    PathSet& w;
+    hipStream_t sA, sB;
+    Wave Wv{};
+    PathLanes PL{};   // k_path's per-lane state and spill columns (the path kernel, hybrid batches)
+    SpillArea sp_path{nullptr, 0}, sp_ext{nullptr, 0}, sp_sh{nullptr, 0};
+    Ahead AH{};
+    hipEvent_t prev_acc = nullptr;  // the previous framebuffer operation: this batch's first accumulate waits for it, once
+};
+// The allocations that follow the plan: the path set, the light vertices, k_path's lanes, the snapshots.
+static khp_status reserve_batch(khp_ctx* c, const BatchPlan& pl, const khp_render_params* p, bool fused,
+                                BatchTarget& B) {
+    PathSet& w = B.w;
     // a partial batch (flushed by a sync) reserves room for a full one, so the
     // first full batch does not allocate
     // (automatic chunks may reach 5/4 of the cap, see above)
-    size_t want = (size_t)P_chunk * S_chunk * nf;
-    if (ops && nf > 1) {
-        const uint32_t fuse = std::max<uint32_t>(1, std::min<uint32_t>(c->prm.fuse_frames, KHP_MAX_FUSE));
-        want = std::max(want, std::min<size_t>(chunk_most(c) / sh_per_path, (size_t)P_all * S_chunk * fuse));
-    }
-    PathSet& w = c->ps[slot];
-    s = ensure_wave(c, w, want, sh_per_path);
-    if (s != KHP_OK) return s;
+    size_t want = (size_t)pl.P_chunk * pl.S_chunk * pl.nf;
+    if (fused && pl.nf > 1)
+        want = std::max(want, std::min<size_t>(chunk_most(c) / pl.sh_per_path, (size_t)pl.P_all * pl.S_chunk * fuse_limit(c)));
+    KHPCHK(ensure_wave(c, w, want, pl.sh_per_path));
     // light subpaths of a chunk: one per (frame, sample slot, subpath, light); k_light_paths
     // indexes them with 32 bits, and their vertices (48 B each) must fit beside the path sets
-    size_t lv_bytes = 0;
-    if (bdm) {
-        const uint64_t nsub = (uint64_t)nf * S_chunk * c->bd.light_paths * (uint64_t)c->S.n_lights;
+    if (pl.bdm) {
+        const uint64_t nsub = (uint64_t)pl.nf * pl.S_chunk * c->bd.light_paths * (uint64_t)c->S.n_lights;
         if (nsub >= ((uint64_t)1 << 31))
             return fail(KHP_EINVAL, "light-path variant: frames x samples x light_paths x lights per chunk reaches "
                                     "2^31 subpaths; lower light_paths or the samples per pass");
-        lv_bytes = (size_t)nsub * c->bd.vertices * 48;
+        const size_t lv_bytes = (size_t)nsub * c->bd.vertices * 48;
         if (lv_bytes > w.lvb.bytes) {
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && lv_bytes + (lv_bytes >> 3) > free_b)
@@ -4081,70 +4110,375 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
         }
         HIPCHK(w.lvb.ensure(lv_bytes));
     }
-    const size_t call_paths = (size_t)P_all * p->spp * nf;
-    const bool use_path = path_ok && (c->prm.path_kernel == 2 ||
-                                      (c->prm.path_kernel == 0 && !async && call_paths <= PATH_AUTO_MAX));
-    const bool path_wide = use_path && c->S.wide != nullptr && c->prm.wide_from == 0;
-    // hybrid batches (khp_ctx_params.path_from): a wavefront render hands the paths still
-    // alive at bounce path_from to one k_path launch, which carries them through the
-    // remaining bounces without a barrier per bounce (not with the light-path variant,
-    // hit sorting, instrumented renders or queue dumps)
-    const uint32_t hyb_from = (!use_path && path_ok && c->prm.path_from > 0 && c->prm.path_from < p->depth)
-                              ? c->prm.path_from : 0u;
-    const bool hyb_wide = hyb_from > 0 && c->S.wide != nullptr && hyb_from >= c->prm.wide_from;
-    PathLanes PL{};
-    SpillArea sp_path{nullptr, 0};
-    if (use_path || hyb_from > 0) {
+    if (pl.use_path || pl.hyb_from > 0) {
         const size_t lanes = (size_t)c->grid_path * TRAV_BLOCK;
         HIPCHK(w.plane.ensure(lanes * 8 * sizeof(float4)));
         HIPCHK(w.pspill.ensure(lanes * STACK_MAX * sizeof(int4)));
-        for (int k = 0; k < 8; ++k) PL.col[k] = w.plane.as<float4>() + (size_t)k * lanes;
-        sp_path = SpillArea{w.pspill.as<int4>(), (uint32_t)lanes};
+        for (int k = 0; k < 8; ++k) B.PL.col[k] = w.plane.as<float4>() + (size_t)k * lanes;
+        B.sp_path = SpillArea{w.pspill.as<int4>(), (uint32_t)lanes};
     }
-    const int grid_path = std::max(1, ((path_wide || hyb_wide) ? c->grid_path_w : c->grid_path) / G);
-    const bool lobes_on = c->S.hair_lobes != HAIR_LOBE_R;   // khp_set_hair_lobes: the KINDS_LOBES instances
-    if (stats) {
-        const size_t chunks = (size_t)((P_all + P_chunk - 1) / P_chunk) * ((p->spp + S_chunk - 1) / S_chunk);
+    if (pl.stats) {
+        const size_t chunks = (size_t)((pl.P_all + pl.P_chunk - 1) / pl.P_chunk) * ((p->spp + pl.S_chunk - 1) / pl.S_chunk);
         HIPCHK(c->snap.ensure(std::max<size_t>(1, chunks * p->depth) * sizeof(Counters)));
     }
-    // Two streams: A runs generate / extend / shade / accumulate, B runs the
-    // shadow stage (k_shadow + k_shadow_finish) of bounce b while A already
-    // traverses bounce b+1, so each persistent kernel's tail fills with the
-    // other's blocks.  Ordering: B(b) after shade(b) on A; shade(b+1) after
-    // B(b) (both update the path colour C in bounce order); the shadow queue
-    // of bounce b+2 reuses parity b's buffers only after shade(b+1), which
-    // already waited for B(b).  Instrumented renders run everything on the
-    // context stream so the per-bounce snapshots are exact.
-    const bool overlap = !stats && !c->prm.serial_stages;
-    hipStream_t sA = overlap ? w.sA : c->stream;
-    hipStream_t sB = overlap ? w.sB : c->stream;
+    B.sp_ext = SpillArea{w.spill.as<int4>(), (uint32_t)c->grid_ext_max * TRAV_BLOCK};
+    B.sp_sh = SpillArea{w.spill_sh.as<int4>(), (uint32_t)c->grid_sh * TRAV_BLOCK};
+    return KHP_OK;
+}
+// Record a no-timing event of the slot on a stream ...
+static hipError_t mark_stream(FrameSlot& f, hipStream_t on, hipEvent_t& e) {
+    return hipEventRecord(e = slot_event(f.sync_pool, f.sync_next, true), on);
+}
+// ... and make another stream wait for it: what follows on `to` runs after what `from` holds now.
+static khp_status order_after(FrameSlot& f, hipStream_t from, hipStream_t to) {
+    hipEvent_t e;
+    HIPCHK(mark_stream(f, from, e));
+    HIPCHK(hipStreamWaitEvent(to, e, 0));
+    return KHP_OK;
+}
+// Retarget a Wave at the regrouped ray columns of parity cur (rs_cols, rs_qsrc): ray
+// columns and state slots as k_extend takes them; the state itself stays put.
+static void use_sorted_columns(Wave& W, PathSet& w, int cur) {
+    const size_t cp = w.cap;
+    for (int k = 0; k < 3; ++k) {
+        W.qo[cur][k] = w.rs_cols.as<float>() + k * cp;
+        W.qd[cur][k] = w.rs_cols.as<float>() + (3 + k) * cp;
+    }
+    W.qpid[cur] = w.rs_cols.as<uint32_t>() + 6 * cp;
+    W.qsrc = w.rs_qsrc.as<uint32_t>();
+}
+// khp_ctx_params.dump_bounce: the extension queue of parity cur into c->dump, front part, then back part
+static khp_status dump_extension_queue(khp_ctx* c, const Wave& Wv, int cur, hipStream_t sA) {
+    uint32_t nq[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(&nq[0], &Wv.cnt->nq[cur], 4, hipMemcpyDeviceToHost, sA));
+    HIPCHK(hipMemcpyAsync(&nq[1], &Wv.cnt->nqb[cur], 4, hipMemcpyDeviceToHost, sA));
+    KHPCHK(wait_stream(c, sA, "the queue dump"));
+    const size_t m = (size_t)nq[0] + nq[1];
+    c->dump.resize(6 * m);
+    for (int q = 0; q < 6; ++q) {
+        const float* col = q < 3 ? Wv.qo[cur][q] : Wv.qd[cur][q - 3];
+        float* dst = c->dump.data() + (size_t)q * m;
+        HIPCHK(hipMemcpy(dst, col, 4 * (size_t)nq[0], hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dst + nq[0], col + (Wv.cap - nq[1]), 4 * (size_t)nq[1], hipMemcpyDeviceToHost));
+    }
+    return KHP_OK;
+}
+// ... and the shadow rays that bounce's shade queued (Wb: its view), o, d, t_max each, into c->dump_sh
+static khp_status dump_shadow_queue(khp_ctx* c, const Wave& Wb, hipStream_t sA) {
+    KHPCHK(wait_stream(c, sA, "the queue dump"));
+    ShadowQ hq;
+    HIPCHK(hipMemcpy(&hq, Wb.shq, sizeof(ShadowQ), hipMemcpyDeviceToHost));
+    const size_t R = Wb.shs;   // float4 per record
+    std::vector<float4> rec(R * ((size_t)hq.nsh + hq.nshb));
+    if (hq.nsh) HIPCHK(hipMemcpy(rec.data(), Wb.sh, R * sizeof(float4) * hq.nsh, hipMemcpyDeviceToHost));
+    if (hq.nshb)
+        HIPCHK(hipMemcpy(rec.data() + R * (size_t)hq.nsh, Wb.sh + R * (Wb.cap - hq.nshb),
+                         R * sizeof(float4) * hq.nshb, hipMemcpyDeviceToHost));
+    c->dump_sh.resize(7 * ((size_t)hq.nsh + hq.nshb));
+    for (size_t k = 0; k < (size_t)hq.nsh + hq.nshb; ++k) {
+        const float4 a = rec[R * k], d = rec[R * k + 1];
+        const float v[7] = {a.x, a.y, a.z, d.x, d.y, d.z, a.w};
+        memcpy(c->dump_sh.data() + 7 * k, v, sizeof(v));
+    }
+    return KHP_OK;
+}
+// ray sorting: regroup the next bounce's queue (parity cur ^ 1, as shade wrote it) by origin cell
+static khp_status regroup_next_queue(khp_ctx* c, BatchTarget& B, int cur) {
+    PathSet& w = B.w;
+    const hipStream_t sA = B.sA;
+    const size_t cp = w.cap;
+    HIPCHK(w.rs_cols.ensure(7 * cp * sizeof(float)));
+    HIPCHK(w.rs_qsrc.ensure(cp * sizeof(uint32_t)));
+    HIPCHK(w.rs_keys.ensure(cp * sizeof(uint32_t)));
+    HIPCHK(w.rs_hist.ensure(2 * RS_CELLS * sizeof(uint32_t)));
+    uint32_t* hist = w.rs_hist.as<uint32_t>();
+    timed(c, B.f, T_OTHER, true, sA);   // under "other": shade_ms stays k_shade's alone
+    HIPCHK(hipMemsetAsync(hist, 0, RS_CELLS * sizeof(uint32_t), sA));
+    const uint32_t rs_per_cu = std::max(1u, std::min(2048u / RS_THREADS, 163840u / (RS_CELLS * 4u)));
+    const dim3 rs_grid((c->n_cu > 0 ? (uint32_t)c->n_cu : 256u) * rs_per_cu);   // resident blocks
+    hipLaunchKernelGGL(k_rsort_count, rs_grid, dim3(RS_THREADS), 0, sA, c->S, B.Wv, cur ^ 1, hist,
+                       w.rs_keys.as<uint32_t>());
+    hipLaunchKernelGGL(k_rsort_scan, dim3(1), dim3(1024), 0, sA, hist, hist + RS_CELLS);
+    hipLaunchKernelGGL(k_rsort_scatter, rs_grid, dim3(RS_THREADS), 0, sA, B.Wv, cur ^ 1,
+                       w.rs_keys.as<uint32_t>(), hist + RS_CELLS, w.rs_cols.as<float>(),
+                       w.rs_qsrc.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    timed(c, B.f, T_OTHER, false, sA);
+    return KHP_OK;
+}
+// What one wavefront bounce of a chunk leaves for the next.
+struct BounceCarry {
+    hipEvent_t done_b = nullptr;  // shadow stage of the previous bounce finished (B)
+    bool sorted = false;          // this bounce's queue was regrouped by origin cell (rs_*)
+    bool prepped = false;         // this bounce's k_prep was enqueued before the previous fork
+};
+// Bounce b of the chunk B.Wv: extend and shade on stream A, the shadow stage on B.
+// dump: this is the bounce and chunk whose queues khp_ctx_params.dump_bounce asks for.
+static khp_status enqueue_bounce(khp_ctx* c, const BatchPlan& pl, const khp_render_params* p, BatchTarget& B,
+                                 uint32_t b, bool dump, BounceCarry& k) {
+    FrameSlot& f = B.f;
+    PathSet& w = B.w;
+    const Wave& Wv = B.Wv;
+    const hipStream_t sA = B.sA, sB = B.sB;
+    const int cur = b & 1;
+    c->cur_bounce = (int)b;
+    Wave Wb = Wv;
+    if (k.sorted) use_sorted_columns(Wb, w, cur);
+    Wb.sh = w.shb[cur].as<float4>();
+    Wb.vis = w.visb[cur].as<uint8_t>();
+    Wb.shq = w.shqb.as<ShadowQ>() + cur;
+    if (dump) KHPCHK(dump_extension_queue(c, Wv, cur, sA));
+    if (!k.prepped) hipLaunchKernelGGL(k_prep, dim3(1), dim3(1), 0, sA, Wv.cnt, Wb.shq, cur);
+    k.prepped = false;
+#ifdef KHP_LEAF_REUSE
+    if (pl.stats) HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_reuse_b), &b, sizeof(b), 0, hipMemcpyHostToDevice, sA));
+#endif
+    timed(c, f, T_EXTEND, true, sA);
+    const bool cam = b == 0 && Wv.cam0;
+    const bool wide = c->S.wide != nullptr && b >= c->prm.wide_from;
+    launch_extend(pl.stats, cam, wide, wide ? pl.grid_ext_w : cam ? pl.grid_ext_cam : pl.grid_ext, sA, c->S, Wb, cur,
+                  B.sp_ext, c->prm.lds_nodes != 0);
+    timed(c, f, T_EXTEND, false, sA);
+    if (k.done_b && sB != sA) HIPCHK(hipStreamWaitEvent(sA, k.done_b, 0));
+    timed(c, f, T_SHADE, true, sA);
+    if (Wb.perm) {  // hit sorting (shade_order 1): part of the shade time
+        HIPCHK(hipMemsetAsync(Wb.hcls, 0, 32 * sizeof(uint32_t), sA));
+        hipLaunchKernelGGL(k_hit_class, dim3(c->grid_shade), dim3(256), 0, sA, c->S, Wb, cur);
+        hipLaunchKernelGGL(k_hit_scatter, dim3(c->grid_shade), dim3(256), 0, sA, Wb, cur);
+    }
+    launch_shade(c->S.textured != 0, pl.bdm, pl.fur_only, pl.lobes_on, c->grid_shade, c->grid_shade_bd, sA, c->S, Wb,
+                 cur, b);
+    timed(c, f, T_SHADE, false, sA);
+    k.sorted = pl.rs_from > 0 && b + 1 >= pl.rs_from && b + 1 < p->depth;
+    if (k.sorted) KHPCHK(regroup_next_queue(c, B, cur));   // before the shadow stage forks: alone on the chip it takes
+                                                           // ~0.2 ms per frame, beside the shadow stage's persistent grid ~2 ms
+    if (!pl.stats && sB != sA && b + 1 < p->depth) {
+        // the next bounce's counter reset before the fork, so its k_extend is ready on
+        // stream A when the shadow stage becomes ready on B (the queues it resets are
+        // consumed: this bounce's, and the previous bounce's shadow queue, which
+        // k_shade waited for); +0.4%, profiles/r05ad_early_prep_ab.txt.  Instrumented
+        // renders keep the reset at the bounce's start (per-bounce counter snapshots)
+        hipLaunchKernelGGL(k_prep, dim3(1), dim3(1), 0, sA, Wv.cnt, w.shqb.as<ShadowQ>() + (cur ^ 1), cur ^ 1);
+        k.prepped = true;
+    }
+    if (sB != sA) KHPCHK(order_after(f, sA, sB));   // the shadow stage after this bounce's shade
+    if (dump) KHPCHK(dump_shadow_queue(c, Wb, sA));
+    timed(c, f, T_SHADOW, true, sB);
+    const bool wide_sh = c->S.wide != nullptr && b >= std::max(c->prm.wide_from, (uint32_t)KHP_WIDE_SH_FROM);
+    launch_shadow(pl.stats, wide_sh, wide_sh ? pl.grid_sh_w : pl.grid_sh, sB, c->S, Wb, B.sp_sh, c->prm.lds_nodes != 0);
+    timed(c, f, T_SHADOW, false, sB);
+    timed(c, f, T_SHADOW_FINISH, true, sB);   // shadow stage = any-hit traversal + finish
+    if (pl.bdm) hipLaunchKernelGGL(k_shadow_finish<true>, dim3(c->grid_fin), dim3(256), 0, sB, c->S, Wb, cur ^ 1);
+    else hipLaunchKernelGGL(k_shadow_finish<false>, dim3(c->grid_fin), dim3(256), 0, sB, c->S, Wb, cur ^ 1);
+    timed(c, f, T_SHADOW_FINISH, false, sB);
+    if (sB != sA) HIPCHK(mark_stream(f, sB, k.done_b));
+    if (pl.stats) {
+        HIPCHK(hipMemcpyAsync(c->snap.as<Counters>() + f.snaps.size(), w.cnt.p, sizeof(Counters),
+                              hipMemcpyDeviceToDevice, sA));
+        f.snaps.push_back(Snap{b});
+    }
+    return KHP_OK;
+}
+
+// Fold the chunk's colours into the framebuffer on stream A: one kernel over all frames and samples where it
+// can, else one k_accumulate per frame, the batch's gathers and snapshots between them where they were called.
+static khp_status enqueue_accumulate(khp_ctx* c, const BatchPlan& pl, const std::vector<PendingOp>* ops,
+                                     BatchTarget& B) {
+    const Wave& Wv = B.Wv;
+    const hipStream_t sA = B.sA;
+    const uint32_t P = Wv.P, ns = Wv.n_samples;
+    timed(c, B.f, T_OTHER, true, sA);
+    if (pl.wa_frames == 1 && pl.only_renders && ns <= ACC_MAX_SAMPLES) {
+        hipLaunchKernelGGL(k_accumulate_all, dim3((P + ACC_PIX - 1) / ACC_PIX), dim3(ACC_PIX),
+                           ACC_PIX * (ns + 1) * sizeof(float4), sA, Wv, c->fb.as<float>());
+    } else if (!ops) {   // this call's frame (frames rendered ahead through fusion wait for their calls)
+        hipLaunchKernelGGL(k_accumulate, dim3((P + 255) / 256), dim3(256), 0, sA, Wv, c->fb.as<float>(), 0u);
+    } else {
+        // fused frames in call order; a gather between two of them runs on the
+        // context stream after the first's accumulate and before the second's
+        // (a batch with gathers is one chunk: flush() checks)
+        uint32_t fr = 0;
+        for (const PendingOp& o : *ops) {
+            if (o.kind == PendingOp::RENDER) {
+                hipLaunchKernelGGL(k_accumulate, dim3((P + 255) / 256), dim3(256), 0, sA, Wv, c->fb.as<float>(), fr++);
+            } else {
+                HIPCHK(mark_stream(B.f, sA, c->fb_evt));
+                KHPCHK(op_now(c, o));   // waits fb_evt, sets fb_evt to its own end
+                HIPCHK(hipStreamWaitEvent(sA, c->fb_evt, 0));
+            }
+        }
+    }
+    timed(c, B.f, T_OTHER, false, sA);
+    return KHP_OK;
+}
+
+// One chunk: the owned pixels from p0 (pl.P_chunk of them at most) x the samples from s0
+// (pl.S_chunk at most) x every fused frame, from camera rays to the accumulate.
+static khp_status enqueue_chunk(khp_ctx* c, const BatchPlan& pl, const khp_render_params* p,
+                                const std::vector<PendingOp>* ops, BatchTarget& B, uint32_t p0, uint32_t s0) {
+    FrameSlot& f = B.f;
+    PathSet& w = B.w;
+    Wave& Wv = B.Wv;
+    const hipStream_t sA = B.sA, sB = B.sB;
+    const uint32_t P = std::min(pl.P_chunk, pl.P_all - p0), ns = std::min(pl.S_chunk, p->spp - s0);
+    Wv.P = P;
+    Wv.p_off = p0;
+    Wv.sample0 = pl.fs0[0] + s0;
+    Wv.n_samples = ns;
+    Wv.n_frames = pl.nf;
+    for (uint32_t q = 0; q < pl.nf; ++q) Wv.fsample0[q] = pl.fs0[q] + s0;
+    const uint32_t npaths = P * ns * pl.nf;
+    if (pl.use_path) {  // every bounce of the chunk's paths in one launch; then the accumulate below
+        HIPCHK(hipMemsetAsync(reinterpret_cast<char*>(Wv.cnt) + offsetof(Counters, fetch_ext), 0,
+                              sizeof(Counters::fetch_ext), sA));
+        timed(c, f, T_OTHER, true, sA);
+        launch_path(c->S.textured != 0, pl.path_wide, pl.fur_only, pl.lobes_on, pl.grid_path, sA, c->S, Wv, B.sp_path,
+                    B.PL, B.AH);
+        HIPCHK(hipGetLastError());
+        if (pl.ahead) ahead_commit(c, p, pl.call_paths);
+        timed(c, f, T_OTHER, false, sA);
+    }
+    timed(c, f, T_OTHER, true, sA);
+    if (!pl.use_path && Wv.cam0) hipLaunchKernelGGL(k_start, dim3(1), dim3(1), 0, sA, Wv.cnt, npaths);
+    else if (!pl.use_path) hipLaunchKernelGGL(k_generate, dim3((npaths + 255) / 256), dim3(256), 0, sA, c->S, Wv);
+    if (pl.bdm) {  // the light subpaths of this chunk's sample slots (frames x samples)
+        const uint32_t nsub = pl.nf * ns * c->bd.light_paths * (uint32_t)c->S.n_lights;
+        hipLaunchKernelGGL(k_light_paths, dim3((nsub + 63) / 64), dim3(64), 0, sA, c->S, Wv);
+    }
+    timed(c, f, T_OTHER, false, sA);
+    if (pl.bdm && c->bd.image_plane) {
+        // shadeBDPTImagePlane before bounce 0, all on stream A: connection groups
+        // on the parity-1 shadow buffers, traced, and added to the bounce-0 state
+        Wave Wi = Wv;
+        Wi.sh = w.shb[1].as<float4>();
+        Wi.vis = w.visb[1].as<uint8_t>();
+        Wi.shq = w.shqb.as<ShadowQ>() + 1;
+        HIPCHK(hipMemsetAsync(Wi.shq, 0, sizeof(ShadowQ), sA));
+        hipLaunchKernelGGL(k_img_connect, dim3((npaths + 255) / 256), dim3(256), 0, sA, c->S, Wi);
+        timed(c, f, T_SHADOW, true, sA);
+        launch_shadow(pl.stats, false, pl.grid_sh, sA, c->S, Wi, B.sp_sh);
+        timed(c, f, T_SHADOW, false, sA);
+        timed(c, f, T_SHADOW_FINISH, true, sA);
+        hipLaunchKernelGGL(k_shadow_finish<true>, dim3(c->grid_fin), dim3(256), 0, sA, c->S, Wi, 0);
+        timed(c, f, T_SHADOW_FINISH, false, sA);
+    }
+    BounceCarry k;
+    const uint32_t b_stop = pl.use_path ? 0u : pl.hyb_from > 0 ? pl.hyb_from : p->depth;   // wavefront bounces
+    for (uint32_t b = 0; b < b_stop; ++b)
+        KHPCHK(enqueue_bounce(c, pl, p, B, b, pl.dump_b == (int)b && p0 == 0 && s0 == 0, k));
+    if (pl.hyb_from > 0) {   // the remaining bounces of the paths in the bounce-hyb_from queue
+        const int cur = pl.hyb_from & 1;
+        Wave Wq = Wv;
+        if (k.sorted) use_sorted_columns(Wq, w, cur);
+        Wq.q_cur = (uint32_t)cur;
+        Wq.q_bounce = pl.hyb_from;
+        if (k.done_b && sB != sA) HIPCHK(hipStreamWaitEvent(sA, k.done_b, 0));   // the deferred colour adds
+        if (!k.prepped) hipLaunchKernelGGL(k_prep, dim3(1), dim3(1), 0, sA, Wv.cnt, w.shqb.as<ShadowQ>() + cur, cur);
+        c->cur_bounce = (int)pl.hyb_from;
+        timed(c, f, T_OTHER, true, sA);
+        launch_path(c->S.textured != 0, pl.hyb_wide, pl.fur_only, pl.lobes_on, pl.grid_path, sA, c->S, Wq, B.sp_path,
+                    B.PL, Ahead{}, true);
+        HIPCHK(hipGetLastError());
+        timed(c, f, T_OTHER, false, sA);
+    }
+    c->cur_bounce = -1;
+    if (k.done_b) HIPCHK(hipStreamWaitEvent(sA, k.done_b, 0));
+    if (B.prev_acc) {  // framebuffer order: previous frame
+        HIPCHK(hipStreamWaitEvent(sA, B.prev_acc, 0));
+        B.prev_acc = nullptr;
+    }
+    KHPCHK(enqueue_accumulate(c, pl, ops, B));
+    // the next chunk's shadow stages come after this chunk's accumulate
+    if (sB != sA) KHPCHK(order_after(f, sA, sB));
+    return KHP_OK;
+}
+
+// Open a batch: complete what must complete first, open the report, serve a pass that was
+// rendered ahead, make the framebuffer and pixel list, and take the frame slot.
+static khp_status open_batch(khp_ctx* c, const khp_render_params* p, float* out_rgb, bool single, BatchOpening& o) {
+    const bool stats = render_stats(c, p), async = render_async(p);
+    const size_t npix = (size_t)p->width * p->height;
+    o.geometry_change = c->fbW != p->width || c->fbH != p->height || !c->fb.p || !(tile_key(*p) == c->pix_key) ||
+                        !c->pix.p;
+    if (!async || o.geometry_change) {  // a synchronous render (or new buffers) first completes the in-flight frames
+        KHPCHK(drain(c));
+        // An asynchronous frame on new buffers keeps accumulating into the
+        // report opened since the last khp_sync; only a synchronous render
+        // starts a fresh one.
+        if (!async) c->report_open = false;
+    }
+    if (!async || !c->report_open) report_begin(c);
+    // render-ahead through fusion (c->wa): a synchronous single pass that an earlier
+    // call already rendered only accumulates; every other render drops the batch
+    o.sync1 = !async && single;
+    o.continues = o.sync1 && is_expected(c->series, c, *p);
+    c->series.valid = false;
+    if (o.sync1 && !stats && is_expected(c->wa.next, c, *p) && c->fb.p && c->fbW == p->width && c->fbH == p->height) {
+        o.served = true;
+        return wave_ahead_hit(c, p, out_rgb);
+    }
+    c->wa.next.valid = false;
+    if (c->fbW != p->width || c->fbH != p->height || !c->fb.p) {
+        HIPCHK(c->fb.ensure(npix * 3 * sizeof(float)));
+        HIPCHK(hipMemsetAsync(c->fb.p, 0, npix * 3 * sizeof(float), c->stream));
+        HIPCHK(c->pixheavy.ensure(npix));
+        HIPCHK(hipMemsetAsync(c->pixheavy.p, 0, npix, c->stream));
+        c->fbW = p->width;
+        c->fbH = p->height;
+    }
+    KHPCHK(prepare_pixels(c, p));
+    if (o.geometry_change) KHPCHK(wait_stream(c, c->stream, "the framebuffer setup"));
+    // Batches in flight: an asynchronous render takes the next frame slot (its
+    // own path set and streams) and returns once enqueued; up to
+    // prm.frames_in_flight batches then run at the same time, each persistent
+    // launch taking 1/F of the resident grid.  The framebuffer is written in
+    // render order: each accumulate waits for the previous framebuffer
+    // operation (accumulate or gather).
+    o.slot = async ? (int)(c->frame_no % (uint64_t)frames_in_flight(c)) : 0;
+    c->frame_no += async ? 1 : 0;
+    KHPCHK(harvest(c, o.slot));  // the slot's previous batch (async series)
+    FrameSlot& f = c->fs[o.slot];
+    f.ev_next = f.sync_next = 0;
+    f.launches.clear();
+    f.snaps.clear();
+    return KHP_OK;
+}
+
+// Enqueue one frame, or a fused batch of asynchronous frames (ops: their
+// render operations, which differ only in first_sample, and the framebuffer
+// gathers between them, in call order; p = the first render's parameters).
+static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* out_rgb,
+                                 const std::vector<PendingOp>* ops) {
+    BatchOpening o;
+    KHPCHK(open_batch(c, p, out_rgb, !ops, o));
+    if (o.served) return KHP_OK;
+    BatchPlan pl;
+    KHPCHK(plan_batch(c, p, ops, o, pl));
+    FrameSlot& f = c->fs[o.slot];
+    PathSet& w = c->ps[o.slot];
+    f.nf = pl.nf;
+    BatchTarget B{f, w, nullptr, nullptr};
+    KHPCHK(reserve_batch(c, pl, p, ops != nullptr, B));
+    const hipStream_t sA = B.sA = pl.overlap ? w.sA : c->stream;
+    const hipStream_t sB = B.sB = pl.overlap ? w.sB : c->stream;
     c->cur_bounce = -1;
     f.ev_start = slot_event(f.ev_pool, f.ev_next, false);
     (void)hipEventRecord(f.ev_start, c->stream);
     // Fork from the context stream (framebuffer clears, pixel-list uploads) --
     // not for an asynchronous frame: the context stream also carries the joins
     // of the frames still in flight, and waiting on it would serialise them.
-    if (!async || geometry_change) {
-        hipEvent_t e_fork = slot_event(f.sync_pool, f.sync_next, true);
-        HIPCHK(hipEventRecord(e_fork, c->stream));
+    if (!pl.async || o.geometry_change) {
+        hipEvent_t e_fork;
+        HIPCHK(mark_stream(f, c->stream, e_fork));
         if (sA != c->stream) HIPCHK(hipStreamWaitEvent(sA, e_fork, 0));
         if (sB != c->stream) HIPCHK(hipStreamWaitEvent(sB, e_fork, 0));
     }
-    hipEvent_t prev_acc = c->fb_evt;  // the previous framebuffer operation (this batch's accumulate waits for it)
+    B.prev_acc = c->fb_evt;
     HIPCHK(hipMemsetAsync(w.cnt.p, 0, sizeof(Counters), sA));
     HIPCHK(hipMemsetAsync(w.shqb.p, 0, 2 * sizeof(ShadowQ), sA));
-    if (sB != sA) {
-        hipEvent_t z = slot_event(f.sync_pool, f.sync_next, true);
-        HIPCHK(hipEventRecord(z, sA));
-        HIPCHK(hipStreamWaitEvent(sB, z, 0));
-    }
-    bool acc_waited = false;
-    Wave Wv = wave_view(c, w);
-    // render-ahead (khp_ctx_params.render_ahead): synchronous path-kernel calls of one chunk
-    const bool ahead = use_path && !async && !ops && nf == 1 && c->prm.render_ahead != 0 && P_all > 0 &&
-                       P_chunk >= P_all && S_chunk >= p->spp && call_paths <= (size_t)PID_MASK + 1;
-    Ahead AH{};
-    if (ahead) KHPCHK(ahead_prepare(c, p, call_paths, sA, AH, &Wv.CK));
+    if (sB != sA) KHPCHK(order_after(f, sA, sB));
+    Wave& Wv = B.Wv = wave_view(c, w);
+    if (pl.ahead) KHPCHK(ahead_prepare(c, p, pl.call_paths, sA, B.AH, &Wv.CK));
     Wv.pix = c->pix.as<uint32_t>();
     Wv.W = p->width;
     Wv.H = p->height;
@@ -4152,11 +4486,11 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
     Wv.depth = p->depth;
     Wv.pix_major = c->prm.path_order != 0 ? 1u : 0u;
     Wv.pixheavy = nullptr;
-    if (c->prm.path_order == 2 && !use_path && P_all) {  // heavy-first pixel list (k_pix_order), per path set
-        HIPCHK(w.pixo.ensure((size_t)P_all * sizeof(uint32_t)));
+    if (c->prm.path_order == 2 && !pl.use_path && pl.P_all) {  // heavy-first pixel list (k_pix_order), per path set
+        HIPCHK(w.pixo.ensure((size_t)pl.P_all * sizeof(uint32_t)));
         HIPCHK(w.pixcnt.ensure(2 * sizeof(uint32_t)));
         HIPCHK(hipMemsetAsync(w.pixcnt.p, 0, 2 * sizeof(uint32_t), sA));
-        hipLaunchKernelGGL(k_pix_order, dim3((P_all + 255) / 256), dim3(256), 0, sA, c->pix.as<uint32_t>(), P_all,
+        hipLaunchKernelGGL(k_pix_order, dim3((pl.P_all + 255) / 256), dim3(256), 0, sA, c->pix.as<uint32_t>(), pl.P_all,
                            c->pixheavy.as<uint8_t>(), w.pixo.as<uint32_t>(), w.pixcnt.as<uint32_t>());
         Wv.pix = w.pixo.as<uint32_t>();
         Wv.pixheavy = c->pixheavy.as<uint8_t>();
@@ -4164,323 +4498,40 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
     // camera rays in place at bounce 0 (no generate pass): not for the light-path
     // variant (its image-plane connections add to the queued bounce-0 state) nor
     // when bounce 0's queue is dumped
-    Wv.cam0 = (!bdm && dump_b != 0) ? 1u : 0u;
-    Wv.shs = bdm ? 6u : 4u;   // next-event records are 64 B; the light-path variant's connection records 96
-    Wv.bd = BdptDev{bdm ? 1u : 0u, c->bd.light_paths, (uint32_t)c->S.n_lights, c->bd.vertices, c->bd.bias,
+    Wv.cam0 = (!pl.bdm && pl.dump_b != 0) ? 1u : 0u;
+    Wv.shs = pl.bdm ? 6u : 4u;   // next-event records are 64 B; the light-path variant's connection records 96
+    Wv.bd = BdptDev{pl.bdm ? 1u : 0u, c->bd.light_paths, (uint32_t)c->S.n_lights, c->bd.vertices, c->bd.bias,
                     c->bd.bounce_bias, c->bd.min_pdf, c->bd.image_plane,
-                    bdm ? w.lvb.as<float4>() : nullptr};
-    // ray sorting from bounce rs_from (0: off); not with hit sorting, the light-path
-    // variant or queue dumps, which read the queues in their own order.  Automatic
-    // (ray_sort_from 0): from bounce 2 when the node records exceed RS_AUTO_BYTES --
-    // a cache-resident tree has no misses to save (config 2: -3.6%, config 1: -17%)
-    const uint32_t rs_param = c->prm.ray_sort_from != 0 ? c->prm.ray_sort_from
-                              : (uint64_t)c->n_dnodes * sizeof(DevNode) >= RS_AUTO_BYTES ? 2u : 0u;
-    const uint32_t rs_from = (c->prm.shade_order == 0 && !bdm && dump_b < 0) ? rs_param : 0u;
-    SpillArea sp_ext{w.spill.as<int4>(), (uint32_t)c->grid_ext_max * TRAV_BLOCK};
-    SpillArea sp_sh{w.spill_sh.as<int4>(), (uint32_t)c->grid_sh * TRAV_BLOCK};
-    for (uint32_t p0 = 0; p0 < P_all; p0 += P_chunk) {
-        const uint32_t P = std::min(P_chunk, P_all - p0);
-        for (uint32_t s0 = 0; s0 < p->spp; s0 += S_chunk) {
-            const uint32_t ns = std::min(S_chunk, p->spp - s0);
-            Wv.P = P;
-            Wv.p_off = p0;
-            Wv.sample0 = fs0[0] + s0;
-            Wv.n_samples = ns;
-            Wv.n_frames = nf;
-            for (uint32_t q = 0; q < nf; ++q) Wv.fsample0[q] = fs0[q] + s0;
-            const uint32_t npaths = P * ns * nf;
-            if (use_path) {  // every bounce of the chunk's paths in one launch; then the accumulate below
-                HIPCHK(hipMemsetAsync(reinterpret_cast<char*>(Wv.cnt) + offsetof(Counters, fetch_ext), 0,
-                                      sizeof(Counters::fetch_ext), sA));
-                timed(c, f, 3, true, sA);
-                launch_path(c->S.textured != 0, path_wide, (c->bsdf_kinds & ~KINDS_FUR) == 0u, lobes_on, grid_path, sA,
-                            c->S, Wv, sp_path, PL, AH);
-                HIPCHK(hipGetLastError());
-                if (ahead) ahead_commit(c, p, call_paths);
-                timed(c, f, 3, false, sA);
-            }
-            timed(c, f, 3, true, sA);
-            if (use_path) {
-            } else if (Wv.cam0) hipLaunchKernelGGL(k_start, dim3(1), dim3(1), 0, sA, Wv.cnt, npaths);
-            else hipLaunchKernelGGL(k_generate, dim3((npaths + 255) / 256), dim3(256), 0, sA, c->S, Wv);
-            if (bdm) {  // the light subpaths of this chunk's sample slots (frames x samples)
-                const uint32_t nsub = nf * ns * c->bd.light_paths * (uint32_t)c->S.n_lights;
-                hipLaunchKernelGGL(k_light_paths, dim3((nsub + 63) / 64), dim3(64), 0, sA, c->S, Wv);
-            }
-            timed(c, f, 3, false, sA);
-            if (bdm && c->bd.image_plane) {
-                // shadeBDPTImagePlane before bounce 0, all on stream A: connection groups
-                // on the parity-1 shadow buffers, traced, and added to the bounce-0 state
-                Wave Wi = Wv;
-                Wi.sh = w.shb[1].as<float4>();
-                Wi.vis = w.visb[1].as<uint8_t>();
-                Wi.shq = w.shqb.as<ShadowQ>() + 1;
-                HIPCHK(hipMemsetAsync(Wi.shq, 0, sizeof(ShadowQ), sA));
-                hipLaunchKernelGGL(k_img_connect, dim3((npaths + 255) / 256), dim3(256), 0, sA, c->S, Wi);
-                timed(c, f, 2, true, sA);
-                launch_shadow(stats, false, grid_sh, sA, c->S, Wi, sp_sh);
-                timed(c, f, 2, false, sA);
-                timed(c, f, 4, true, sA);
-                hipLaunchKernelGGL(k_shadow_finish<true>, dim3(c->grid_fin), dim3(256), 0, sA, c->S, Wi, 0);
-                timed(c, f, 4, false, sA);
-            }
-            hipEvent_t done_b = nullptr;  // shadow stage of the previous bounce finished (B)
-            bool sorted = false;          // this bounce's queue was regrouped by origin cell (rs_*)
-            bool prepped = false;         // this bounce's k_prep was enqueued before the previous fork
-            const uint32_t b_stop = use_path ? 0u : hyb_from > 0 ? hyb_from : p->depth;   // wavefront bounces
-            for (uint32_t b = 0; b < b_stop; ++b) {
-                const int cur = b & 1;
-                c->cur_bounce = (int)b;
-                Wave Wb = Wv;
-                if (sorted) {   // the regrouped ray columns replace this parity's; the state stays put
-                    const size_t cp = w.cap;
-                    for (int k = 0; k < 3; ++k) {
-                        Wb.qo[cur][k] = w.rs_cols.as<float>() + k * cp;
-                        Wb.qd[cur][k] = w.rs_cols.as<float>() + (3 + k) * cp;
-                    }
-                    Wb.qpid[cur] = w.rs_cols.as<uint32_t>() + 6 * cp;
-                    Wb.qsrc = w.rs_qsrc.as<uint32_t>();
-                }
-                Wb.sh = w.shb[cur].as<float4>();
-                Wb.vis = w.visb[cur].as<uint8_t>();
-                Wb.shq = w.shqb.as<ShadowQ>() + cur;
-                if (dump_b == (int)b && p0 == 0 && s0 == 0) {  // extension queue: front part, then back part
-                    uint32_t nq[2] = {0, 0};
-                    HIPCHK(hipMemcpyAsync(&nq[0], &Wv.cnt->nq[cur], 4, hipMemcpyDeviceToHost, sA));
-                    HIPCHK(hipMemcpyAsync(&nq[1], &Wv.cnt->nqb[cur], 4, hipMemcpyDeviceToHost, sA));
-                    KHPCHK(wait_stream(c, sA, "the queue dump"));
-                    const size_t m = (size_t)nq[0] + nq[1];
-                    c->dump.resize(6 * m);
-                    for (int q = 0; q < 6; ++q) {
-                        const float* col = q < 3 ? Wv.qo[cur][q] : Wv.qd[cur][q - 3];
-                        float* dst = c->dump.data() + (size_t)q * m;
-                        HIPCHK(hipMemcpy(dst, col, 4 * (size_t)nq[0], hipMemcpyDeviceToHost));
-                        HIPCHK(hipMemcpy(dst + nq[0], col + (Wv.cap - nq[1]), 4 * (size_t)nq[1], hipMemcpyDeviceToHost));
-                    }
-                }
-                if (!prepped) hipLaunchKernelGGL(k_prep, dim3(1), dim3(1), 0, sA, Wv.cnt, Wb.shq, cur);
-                prepped = false;
-#ifdef KHP_LEAF_REUSE
-                if (stats) HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_reuse_b), &b, sizeof(b), 0, hipMemcpyHostToDevice, sA));
-#endif
-                timed(c, f, 0, true, sA);
-                const bool cam = b == 0 && Wv.cam0;
-                const bool wide = c->S.wide != nullptr && b >= c->prm.wide_from;
-                launch_extend(stats, cam, wide, wide ? grid_ext_w : cam ? grid_ext_cam : grid_ext, sA, c->S, Wb, cur,
-                              sp_ext, c->prm.lds_nodes != 0);
-                timed(c, f, 0, false, sA);
-                if (done_b && sB != sA) HIPCHK(hipStreamWaitEvent(sA, done_b, 0));
-                timed(c, f, 1, true, sA);
-                if (Wb.perm) {  // hit sorting (shade_order 1): part of the shade time
-                    HIPCHK(hipMemsetAsync(Wb.hcls, 0, 32 * sizeof(uint32_t), sA));
-                    hipLaunchKernelGGL(k_hit_class, dim3(c->grid_shade), dim3(256), 0, sA, c->S, Wb, cur);
-                    hipLaunchKernelGGL(k_hit_scatter, dim3(c->grid_shade), dim3(256), 0, sA, Wb, cur);
-                }
-                if (lobes_on && c->S.textured)   // TT / TRT compiled in (never with the light-path variant)
-                    hipLaunchKernelGGL((k_shade<true, false, KINDS_ALL | KINDS_LOBES>), dim3(c->grid_shade), dim3(shade_block<true, false>()), 0, sA,
-                                       c->S, Wb, cur, b);
-                else if (lobes_on && (c->bsdf_kinds & ~KINDS_FUR) == 0u)
-                    hipLaunchKernelGGL((k_shade<false, false, KINDS_FUR | KINDS_LOBES>), dim3(c->grid_shade), dim3(shade_block<false, false>()), 0,
-                                       sA, c->S, Wb, cur, b);
-                else if (lobes_on)
-                    hipLaunchKernelGGL((k_shade<false, false, KINDS_ALL | KINDS_LOBES>), dim3(c->grid_shade), dim3(shade_block<false, false>()), 0,
-                                       sA, c->S, Wb, cur, b);
-                else if (c->S.textured && bdm)
-                    hipLaunchKernelGGL((k_shade<true, true>), dim3(c->grid_shade_bd), dim3(shade_block<true, true>()), 0, sA, c->S, Wb, cur, b);
-                else if (c->S.textured)
-                    hipLaunchKernelGGL((k_shade<true, false>), dim3(c->grid_shade), dim3(shade_block<true, false>()), 0, sA, c->S, Wb, cur, b);
-                else if (bdm)
-                    hipLaunchKernelGGL((k_shade<false, true>), dim3(c->grid_shade_bd), dim3(shade_block<false, true>()), 0, sA, c->S, Wb, cur, b);
-                else if ((c->bsdf_kinds & ~KINDS_FUR) == 0u)   // fur scenes: the other BSDF kinds compiled out
-                    hipLaunchKernelGGL((k_shade<false, false, KINDS_FUR>), dim3(c->grid_shade), dim3(shade_block<false, false>()), 0, sA, c->S, Wb,
-                                       cur, b);
-                else
-                    hipLaunchKernelGGL((k_shade<false, false>), dim3(c->grid_shade), dim3(shade_block<false, false>()), 0, sA, c->S, Wb, cur, b);
-                timed(c, f, 1, false, sA);
-                // ray sorting: regroup the next bounce's queue by origin cell
-                auto sort_next = [&]() -> khp_status {
-                    sorted = rs_from > 0 && b + 1 >= rs_from && b + 1 < p->depth;
-                    if (sorted) {
-                        const size_t cp = w.cap;
-                        HIPCHK(w.rs_cols.ensure(7 * cp * sizeof(float)));
-                        HIPCHK(w.rs_qsrc.ensure(cp * sizeof(uint32_t)));
-                        HIPCHK(w.rs_keys.ensure(cp * sizeof(uint32_t)));
-                        HIPCHK(w.rs_hist.ensure(2 * RS_CELLS * sizeof(uint32_t)));
-                        uint32_t* hist = w.rs_hist.as<uint32_t>();
-                        Wave Wn = Wv;   // the next queue (parity cur ^ 1) as shade wrote it
-                        timed(c, f, 3, true, sA);   // under "other": shade_ms stays k_shade's alone
-                        HIPCHK(hipMemsetAsync(hist, 0, RS_CELLS * sizeof(uint32_t), sA));
-                        const uint32_t rs_per_cu = std::max(1u, std::min(2048u / RS_THREADS, 163840u / (RS_CELLS * 4u)));
-                        const dim3 rs_grid((c->n_cu > 0 ? (uint32_t)c->n_cu : 256u) * rs_per_cu);   // resident blocks
-                        hipLaunchKernelGGL(k_rsort_count, rs_grid, dim3(RS_THREADS), 0, sA, c->S, Wn, cur ^ 1, hist,
-                                           w.rs_keys.as<uint32_t>());
-                        hipLaunchKernelGGL(k_rsort_scan, dim3(1), dim3(1024), 0, sA, hist, hist + RS_CELLS);
-                        hipLaunchKernelGGL(k_rsort_scatter, rs_grid, dim3(RS_THREADS), 0, sA, Wn, cur ^ 1,
-                                           w.rs_keys.as<uint32_t>(), hist + RS_CELLS, w.rs_cols.as<float>(),
-                                           w.rs_qsrc.as<uint32_t>());
-                        HIPCHK(hipGetLastError());
-                        timed(c, f, 3, false, sA);
-                    }
-                    return KHP_OK;
-                };
-                KHPCHK(sort_next());   // before the shadow stage forks: alone on the chip it takes ~0.2 ms
-                                       // per frame, beside the shadow stage's persistent grid ~2 ms
-                if (!stats && sB != sA && b + 1 < p->depth) {
-                    // the next bounce's counter reset before the fork, so its k_extend is ready on
-                    // stream A when the shadow stage becomes ready on B (the queues it resets are
-                    // consumed: this bounce's, and the previous bounce's shadow queue, which
-                    // k_shade waited for); +0.4%, profiles/r05ad_early_prep_ab.txt.  Instrumented
-                    // renders keep the reset at the bounce's start (per-bounce counter snapshots)
-                    hipLaunchKernelGGL(k_prep, dim3(1), dim3(1), 0, sA, Wv.cnt, w.shqb.as<ShadowQ>() + (cur ^ 1),
-                                       cur ^ 1);
-                    prepped = true;
-                }
-                if (sB != sA) {
-                    hipEvent_t shaded = slot_event(f.sync_pool, f.sync_next, true);
-                    HIPCHK(hipEventRecord(shaded, sA));
-                    HIPCHK(hipStreamWaitEvent(sB, shaded, 0));
-                }
-                if (dump_b == (int)b && p0 == 0 && s0 == 0) {  // this bounce's shadow rays: o, d, t_max
-                    KHPCHK(wait_stream(c, sA, "the queue dump"));
-                    ShadowQ hq;
-                    HIPCHK(hipMemcpy(&hq, Wb.shq, sizeof(ShadowQ), hipMemcpyDeviceToHost));
-                    const size_t R = Wv.shs;   // float4 per record
-                    std::vector<float4> rec(R * ((size_t)hq.nsh + hq.nshb));
-                    if (hq.nsh)
-                        HIPCHK(hipMemcpy(rec.data(), Wb.sh, R * sizeof(float4) * hq.nsh, hipMemcpyDeviceToHost));
-                    if (hq.nshb)
-                        HIPCHK(hipMemcpy(rec.data() + R * (size_t)hq.nsh, Wb.sh + R * (Wv.cap - hq.nshb),
-                                         R * sizeof(float4) * hq.nshb, hipMemcpyDeviceToHost));
-                    c->dump_sh.resize(7 * ((size_t)hq.nsh + hq.nshb));
-                    for (size_t k = 0; k < (size_t)hq.nsh + hq.nshb; ++k) {
-                        const float4 a = rec[R * k], d = rec[R * k + 1];
-                        const float v[7] = {a.x, a.y, a.z, d.x, d.y, d.z, a.w};
-                        memcpy(c->dump_sh.data() + 7 * k, v, sizeof(v));
-                    }
-                }
-                timed(c, f, 2, true, sB);
-                const bool wide_sh = c->S.wide != nullptr && b >= std::max(c->prm.wide_from, (uint32_t)KHP_WIDE_SH_FROM);
-                launch_shadow(stats, wide_sh, wide_sh ? grid_sh_w : grid_sh, sB, c->S, Wb, sp_sh, c->prm.lds_nodes != 0);
-                timed(c, f, 2, false, sB);
-                timed(c, f, 4, true, sB);   // shadow stage = any-hit traversal + finish
-                if (bdm) hipLaunchKernelGGL(k_shadow_finish<true>, dim3(c->grid_fin), dim3(256), 0, sB, c->S, Wb, cur ^ 1);
-                else hipLaunchKernelGGL(k_shadow_finish<false>, dim3(c->grid_fin), dim3(256), 0, sB, c->S, Wb, cur ^ 1);
-                timed(c, f, 4, false, sB);
-                if (sB != sA) {
-                    done_b = slot_event(f.sync_pool, f.sync_next, true);
-                    HIPCHK(hipEventRecord(done_b, sB));
-                }
-                if (stats) {
-                    HIPCHK(hipMemcpyAsync(c->snap.as<Counters>() + f.snaps.size(), w.cnt.p, sizeof(Counters),
-                                          hipMemcpyDeviceToDevice, sA));
-                    f.snaps.push_back(Snap{b});
-                }
-            }
-            if (hyb_from > 0) {   // the remaining bounces of the paths in the bounce-hyb_from queue
-                const int cur = hyb_from & 1;
-                Wave Wq = Wv;
-                if (sorted) {   // regrouped: ray columns and state slots as k_extend would take them
-                    const size_t cp = w.cap;
-                    for (int k = 0; k < 3; ++k) {
-                        Wq.qo[cur][k] = w.rs_cols.as<float>() + k * cp;
-                        Wq.qd[cur][k] = w.rs_cols.as<float>() + (3 + k) * cp;
-                    }
-                    Wq.qpid[cur] = w.rs_cols.as<uint32_t>() + 6 * cp;
-                    Wq.qsrc = w.rs_qsrc.as<uint32_t>();
-                }
-                Wq.q_cur = (uint32_t)cur;
-                Wq.q_bounce = hyb_from;
-                if (done_b && sB != sA) HIPCHK(hipStreamWaitEvent(sA, done_b, 0));   // the deferred colour adds
-                if (!prepped) hipLaunchKernelGGL(k_prep, dim3(1), dim3(1), 0, sA, Wv.cnt, w.shqb.as<ShadowQ>() + cur, cur);
-                prepped = false;
-                c->cur_bounce = (int)hyb_from;
-                timed(c, f, 3, true, sA);
-                launch_path(c->S.textured != 0, hyb_wide, (c->bsdf_kinds & ~KINDS_FUR) == 0u, lobes_on, grid_path, sA, c->S, Wq,
-                            sp_path, PL, Ahead{}, true);
-                HIPCHK(hipGetLastError());
-                timed(c, f, 3, false, sA);
-            }
-            c->cur_bounce = -1;
-            if (done_b) HIPCHK(hipStreamWaitEvent(sA, done_b, 0));
-            if (prev_acc && !acc_waited) {  // framebuffer order: previous frame
-                HIPCHK(hipStreamWaitEvent(sA, prev_acc, 0));
-                acc_waited = true;
-            }
-            timed(c, f, 3, true, sA);
-            bool only_renders = true;
-            if (ops)
-                for (const PendingOp& o : *ops) only_renders = only_renders && o.kind == PendingOp::RENDER;
-            if (wa_frames > 1) {   // this call's frame; the later frames wait for their calls
-                hipLaunchKernelGGL(k_accumulate, dim3((P + 255) / 256), dim3(256), 0, sA, Wv, c->fb.as<float>(), 0u);
-            } else if ((!ops || only_renders) && ns <= ACC_MAX_SAMPLES) {
-                hipLaunchKernelGGL(k_accumulate_all, dim3((P + ACC_PIX - 1) / ACC_PIX), dim3(ACC_PIX),
-                                   ACC_PIX * (ns + 1) * sizeof(float4), sA, Wv, c->fb.as<float>());
-            } else if (!ops) {
-                hipLaunchKernelGGL(k_accumulate, dim3((P + 255) / 256), dim3(256), 0, sA, Wv, c->fb.as<float>(), 0u);
-            } else {
-                // fused frames in call order; a gather between two of them runs on the
-                // context stream after the first's accumulate and before the second's
-                // (a batch with gathers is one chunk: flush() checks)
-                uint32_t fr = 0;
-                for (const PendingOp& o : *ops) {
-                    if (o.kind == PendingOp::RENDER) {
-                        hipLaunchKernelGGL(k_accumulate, dim3((P + 255) / 256), dim3(256), 0, sA, Wv,
-                                           c->fb.as<float>(), fr++);
-                    } else {
-                        hipEvent_t acc = slot_event(f.sync_pool, f.sync_next, true);
-                        HIPCHK(hipEventRecord(acc, sA));
-                        c->fb_evt = acc;
-                        s = op_now(c, o);   // waits fb_evt, sets fb_evt to its own end
-                        if (s != KHP_OK) return s;
-                        HIPCHK(hipStreamWaitEvent(sA, c->fb_evt, 0));
-                    }
-                }
-            }
-            timed(c, f, 3, false, sA);
-            if (sB != sA) {  // the next chunk's shadow stages come after this chunk's accumulate
-                hipEvent_t acc = slot_event(f.sync_pool, f.sync_next, true);
-                HIPCHK(hipEventRecord(acc, sA));
-                HIPCHK(hipStreamWaitEvent(sB, acc, 0));
-            }
-        }
-    }
-    if (P_all == 0 && ops) {
+                    pl.bdm ? w.lvb.as<float4>() : nullptr};
+    for (uint32_t p0 = 0; p0 < pl.P_all; p0 += pl.P_chunk)
+        for (uint32_t s0 = 0; s0 < p->spp; s0 += pl.S_chunk) KHPCHK(enqueue_chunk(c, pl, p, ops, B, p0, s0));
+    if (pl.P_all == 0 && ops) {
         // a rank that owns no tile runs no chunk, but its gathers and snapshots
         // still take their place in call order (its peers wait for its gathers)
-        for (const PendingOp& o : *ops) {
-            if (o.kind == PendingOp::RENDER) continue;
-            s = op_now(c, o);
-            if (s != KHP_OK) return s;
-        }
+        for (const PendingOp& op : *ops)
+            if (op.kind != PendingOp::RENDER) KHPCHK(op_now(c, op));
         if (c->fb_evt) HIPCHK(hipStreamWaitEvent(sA, c->fb_evt, 0));
     }
-    if (wa_frames > 1) {
-        c->wa.valid = true;
-        c->wa.next = *p;
-        c->wa.next.first_sample = p->first_sample + p->spp;
-        c->wa.gen = c->gen;
+    if (pl.wa_frames > 1) {
+        expect_successor(c->wa.next, c, *p);
         c->wa.Wv = Wv;
-        c->wa.nf = wa_frames;
+        c->wa.nf = pl.wa_frames;
         c->wa.used = 1;
     }
     // join: the batch is done when its last chunk has accumulated
-    hipEvent_t e_end = slot_event(f.sync_pool, f.sync_next, true);
-    HIPCHK(hipEventRecord(e_end, sA));
-    HIPCHK(hipStreamWaitEvent(c->stream, e_end, 0));
+    KHPCHK(order_after(f, sA, c->stream));
     f.done_t = slot_event(f.ev_pool, f.ev_next, false);
     (void)hipEventRecord(f.done_t, c->stream);
-    f.done = slot_event(f.sync_pool, f.sync_next, true);
-    HIPCHK(hipEventRecord(f.done, c->stream));
+    HIPCHK(mark_stream(f, c->stream, f.done));
     c->fb_evt = f.done;
     f.inflight = true;
     HIPCHK(hipGetLastError());
-    if (async) return KHP_OK;
+    if (pl.async) return KHP_OK;
     if (out_rgb && !(p->flags & KHP_RENDER_NO_READBACK)) {
         hipMemcpyKind kind = (p->flags & KHP_RENDER_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        HIPCHK(hipMemcpyAsync(out_rgb, c->fb.p, npix * 3 * sizeof(float), kind, c->stream));
+        HIPCHK(hipMemcpyAsync(out_rgb, c->fb.p, (size_t)p->width * p->height * 3 * sizeof(float), kind, c->stream));
     }
-    s = harvest(c, slot);
-    if (s != KHP_OK) return s;
+    KHPCHK(harvest(c, o.slot));
     KHPCHK(wait_stream(c, c->stream, "a synchronous frame"));
     if (c->ra.counted) {
         c->st.ahead_finished = c->ra.hst[0];
@@ -4488,15 +4539,9 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
         c->ra.counted = false;
     }
     c->report_open = false;
-    if (sync1) {
-        c->series.valid = true;
-        c->series.next = *p;
-        c->series.next.first_sample = p->first_sample + p->spp;
-        c->series.gen = c->gen;
-    }
+    if (pl.sync1) expect_successor(c->series, c, *p);
     return KHP_OK;
 }
-
 
 // Frame fusion (asynchronous renders, khp_ctx_params.fuse_frames = n > 1): up to n
 // consecutive asynchronous frames with the same geometry, spp, depth and seed
@@ -4510,127 +4555,81 @@ static bool fusable(const khp_render_params& a, const khp_render_params& b) {
            a.tile_size == b.tile_size && a.tile_rank == b.tile_rank && a.tile_nranks == b.tile_nranks &&
            a.flags == b.flags;
 }
-
+// The renders among pending operations: how many, and which comes first.
+static size_t renders_in(const std::vector<PendingOp>& ops, const PendingOp** first = nullptr) {
+    size_t nr = 0;
+    for (const PendingOp& o : ops) {
+        if (o.kind != PendingOp::RENDER) continue;
+        if (first && nr == 0) *first = &o;
+        ++nr;
+    }
+    return nr;
+}
+// One group of pending operations, in call order: several renders are one fused batch (their gathers and
+// snapshots inside it); otherwise the operations run one by one, a single render as a batch of its own.
+static khp_status run_group(khp_ctx* c, const std::vector<PendingOp>& grp) {
+    const PendingOp* first = nullptr;
+    if (renders_in(grp, &first) > 1) return enqueue_frames(c, &first->p, nullptr, &grp);
+    for (const PendingOp& o : grp)
+        KHPCHK(o.kind == PendingOp::RENDER ? enqueue_frames(c, &o.p, nullptr, nullptr) : op_now(c, o));
+    return KHP_OK;
+}
+// Cut the pending operations into groups and run them; one group is the common case.
 static khp_status flush(khp_ctx* c) {
     if (c->pend.empty()) return KHP_OK;
     std::vector<PendingOp> ops;
     ops.swap(c->pend);
     const PendingOp* first = nullptr;
-    size_t nr = 0;
-    bool gathers = false;
-    for (const PendingOp& o : ops) {
-        if (o.kind == PendingOp::RENDER) {
-            if (!first) first = &o;
-            ++nr;
-        } else {
-            gathers = true;
-        }
-    }
-    if (!first) {  // only gathers / snapshots
-        for (const PendingOp& o : ops) {
-            khp_status s = op_now(c, o);
-            if (s != KHP_OK) return s;
-        }
-        return KHP_OK;
-    }
+    const size_t nr = renders_in(ops, &first);
+    const bool gathers = nr < ops.size();
+    if (!first) return run_group(c, ops);  // only gathers / snapshots
     // a batch with gathers or snapshots must fit one chunk (every frame accumulated
     // before the next frame's gather); otherwise it is split into one-chunk groups
-    const uint32_t T = first->p.tile_size ? first->p.tile_size : 64;
-    std::vector<uint32_t> tmp;
-    size_t P = 0;
-    {
-        uint32_t nranks = first->p.tile_nranks > 1 ? first->p.tile_nranks : 1;
-        uint32_t pkey[5] = {first->p.width, first->p.height, T, nranks > 1 ? first->p.tile_rank : 0u, nranks};
-        if (memcmp(pkey, c->pix_key, sizeof(pkey)) == 0 && c->pix.p) {
-            P = c->pix_host.size();
-        } else {
-            owned_pixels(first->p.width, first->p.height, T, nranks > 1 ? first->p.tile_rank : 0u, nranks, tmp);
-            P = tmp.size();
-        }
+    size_t P = c->pix_host.size();
+    const TileKey key = tile_key(first->p);
+    if (!(key == c->pix_key && c->pix.p)) {
+        std::vector<uint32_t> tmp;
+        key.pixels(tmp);
+        P = tmp.size();
     }
-    const uint32_t sh_per_path = (c->bd.enabled != 0 && c->S.n_lights > 0) ? c->bd.vertices : 1u;
-    const size_t cap_paths = chunk_most(c) / sh_per_path;
+    const size_t cap_paths = chunk_most(c) / shadow_records_per_path(c);
     const bool one_chunk = P * (size_t)first->p.spp * nr <= cap_paths;
-    if (nr == 1 || !gathers || one_chunk) {
-        if (nr == 1) {
-            for (const PendingOp& o : ops) {
-                khp_status s = o.kind == PendingOp::RENDER ? enqueue_frames(c, &o.p, nullptr, nullptr)
-                                                           : op_now(c, o);
-                if (s != KHP_OK) return s;
-            }
-            return KHP_OK;
-        }
-        return enqueue_frames(c, &first->p, nullptr, &ops);
-    }
+    if (nr == 1 || !gathers || one_chunk) return run_group(c, ops);
     // gathers in a batch larger than one chunk: split it into consecutive
     // groups of as many frames as one chunk holds (each with its gathers)
     const size_t per_group = std::max<size_t>(1, cap_paths / std::max<size_t>(1, P * (size_t)first->p.spp));
     std::vector<PendingOp> grp;
     size_t g_r = 0;
-    auto run = [&]() -> khp_status {
-        khp_status s = KHP_OK;
-        if (g_r == 1) {
-            for (const PendingOp& o : grp) {
-                s = o.kind == PendingOp::RENDER ? enqueue_frames(c, &o.p, nullptr, nullptr) : op_now(c, o);
-                if (s != KHP_OK) break;
-            }
-        } else if (g_r > 1) {
-            const PendingOp* f0 = nullptr;
-            for (const PendingOp& o : grp)
-                if (o.kind == PendingOp::RENDER) { f0 = &o; break; }
-            s = enqueue_frames(c, &f0->p, nullptr, &grp);
-        } else {
-            for (const PendingOp& o : grp) {
-                s = op_now(c, o);
-                if (s != KHP_OK) break;
-            }
-        }
-        grp.clear();
-        g_r = 0;
-        return s;
-    };
     for (const PendingOp& o : ops) {
         if (o.kind == PendingOp::RENDER && g_r == per_group) {
-            khp_status s = run();
-            if (s != KHP_OK) return s;
+            KHPCHK(run_group(c, grp));
+            grp.clear();
+            g_r = 0;
         }
         grp.push_back(o);
         g_r += o.kind == PendingOp::RENDER;
     }
-    return run();
+    return run_group(c, grp);
 }
 
 extern "C" khp_status khp_render(khp_ctx* c, const khp_render_params* p, float* out_rgb) {
-    khp_status s = check_params(c, p);
-    if (s != KHP_OK) return s;
+    KHPCHK(check_params(c, p));
     HIPCHK(hipSetDevice(c->device));
-    const bool stats = (c->flags & KHP_CTX_STATS) != 0 || (p->flags & KHP_RENDER_STATS) != 0;
-    const bool async = (p->flags & KHP_RENDER_ASYNC) != 0;
-    if (async && (stats || (out_rgb && !(p->flags & KHP_RENDER_NO_READBACK))))
+    const bool async = render_async(p);
+    if (async && (render_stats(c, p) || (out_rgb && !(p->flags & KHP_RENDER_NO_READBACK))))
         return fail(KHP_EINVAL, "KHP_RENDER_ASYNC renders take no readback and no instrumentation");
-    if (!async) {
-        s = flush(c);
-        if (s != KHP_OK) return s;
-        return enqueue_frames(c, p, out_rgb, nullptr);
-    }
-    const int fuse = (int)std::max<uint32_t>(1, std::min<uint32_t>(c->prm.fuse_frames, KHP_MAX_FUSE));
-    if (fuse <= 1) {
-        s = flush(c);
-        if (s != KHP_OK) return s;
-        return enqueue_frames(c, p, nullptr, nullptr);
+    if (!async || fuse_limit(c) <= 1) {   // a batch of its own, behind whatever waits to be fused
+        KHPCHK(flush(c));
+        return enqueue_frames(c, p, async ? nullptr : out_rgb, nullptr);
     }
     for (const PendingOp& o : c->pend) {
         if (o.kind == PendingOp::RENDER && !fusable(o.p, *p)) {
-            s = flush(c);
-            if (s != KHP_OK) return s;
+            KHPCHK(flush(c));
             break;
         }
     }
     c->pend.push_back(PendingOp{PendingOp::RENDER, *p, 0});
-    size_t nr = 0;
-    for (const PendingOp& o : c->pend) nr += o.kind == PendingOp::RENDER;
-    if ((int)nr >= fuse) return flush(c);
-    return KHP_OK;
+    return renders_in(c->pend) >= fuse_limit(c) ? flush(c) : KHP_OK;
 }
 
 extern "C" void khp_tonemap_defaults(khp_tonemap* t) {
@@ -5137,7 +5136,7 @@ static khp_status trace_persistent_run(khp_ctx* c, uint32_t n, const float* orig
                                        uint8_t* hit_out) {
     const bool shadow = hit_out != nullptr;
     PathSet& w = c->ps[0];
-    c->wa.valid = false;   // the batch query API reuses ps[0]
+    c->wa.next.valid = false;   // the batch query API reuses ps[0]
     khp_status s = ensure_wave(c, w, n);
     if (s != KHP_OK) return s;
     DevMem o, d, tm, t, ob, uv;
@@ -5675,7 +5674,7 @@ static khp_status gather_now(khp_ctx* c, const khp_render_params* p, int root) {
     if (root < 0 || root >= c->nranks) return fail(KHP_EINVAL, "bad root");
     if (p->tile_nranks != (uint32_t)c->nranks) return fail(KHP_EINVAL, "tile_nranks must equal the comm size");
     HIPCHK(hipSetDevice(c->device));
-    uint32_t T = p->tile_size ? p->tile_size : 64;
+    const uint32_t T = tile_key(*p).tile;
     uint32_t key[6] = {p->width, p->height, T, (uint32_t)c->nranks, (uint32_t)c->rank, (uint32_t)root};
     if (memcmp(key, c->gather_key, sizeof(key)) != 0) {
         // the pixel lists depend only on the frame geometry: build + upload once, not per frame
