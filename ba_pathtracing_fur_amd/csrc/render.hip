@@ -2836,6 +2836,7 @@ struct khp_ctx {
     } wa;
     NextCall series;   // the last synchronous single-pass call, first_sample advanced by its spp
     std::shared_ptr<struct AovState> aov;   // khp_render_aov's own scratch (aov.h), made by its first call
+    std::shared_ptr<struct DnState> dn;     // khp_denoise's own scratch (denoise_dev.h), made by its first call
 };
 constexpr size_t LG_SLOTS = 64;
 
@@ -5054,6 +5055,7 @@ extern "C" khp_status khp_debug_queue(khp_ctx* c, uint32_t* n, float* orig, floa
 
 #include "debug_query.h"   // ABI 15: khp_debug_surface / _bsdf_sample / _bsdf_eval / _light_dir / _light_isect
 #include "aov.h"           // khp_render_aov: per-pixel first-hit feature buffers
+#include "denoise_dev.h"   // khp_denoise: the guided a-trous filter over those buffers
 
 extern "C" khp_status khp_read_framebuffer(khp_ctx* c, float* out_rgb) {
     if (c) {  // complete asynchronous frames first

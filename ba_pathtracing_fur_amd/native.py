@@ -160,6 +160,29 @@ AOV_CHANNELS = {"normal": ((3,), np.float32), "albedo": ((3,), np.float32), "tan
                 "depth": ((), np.float32), "coverage": ((), np.float32), "object": ((), np.int32)}
 
 
+DENOISE_DEVICE = 1 << 0
+DENOISE_DEMODULATE = 1 << 1
+
+
+class DenoiseParams(ctypes.Structure):
+    """khp_denoise_params (48 bytes): the guided a-trous filter's size, iterations, flags, sigmas and clamp."""
+    _fields_ = [("width", c_uint32), ("height", c_uint32), ("iterations", c_uint32), ("flags", c_uint32),
+                ("sigma_color", c_float), ("sigma_normal", c_float), ("sigma_tangent", c_float),
+                ("sigma_depth", c_float), ("sigma_coverage", c_float), ("clamp", c_float),
+                ("reserved", c_uint32 * 2)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "DenoiseParams":
+        """khp_denoise_params_defaults (5 iterations, sigmas 4 / 0.35 / 0.35 / 0.05 / 0.25, no clamp) with fields changed."""
+        p = cls()
+        load_library().khp_denoise_params_defaults(ctypes.byref(p))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_) or k == "reserved":
+                raise AttributeError(f"khp_denoise_params has no field {k}")
+            setattr(p, k, v)
+        return p
+
+
 class Tonemap(ctypes.Structure):
     """khp_tonemap: KIRK::Tonemapper's parameters (Utils/Tonemapping.h:22-33)."""
     _fields_ = [("exposure", c_float), ("bias", c_float), ("gamma", c_float), ("contrast", c_float),
@@ -216,7 +239,8 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_fur_count", "khp_gen_fur", "khp_gen_fur_device", "khp_debug_surface", "khp_debug_bsdf_sample",
             "khp_debug_bsdf_eval", "khp_debug_light_dir", "khp_debug_light_isect", "khp_hair_lobes_defaults",
             "khp_set_hair_lobes", "khp_get_hair_lobes", "khp_debug_hair_sample", "khp_render_aov",
-            "khp_debug_light_paths", "khp_debug_bdpt_connect", "khp_debug_img_connect"]
+            "khp_debug_light_paths", "khp_debug_bdpt_connect", "khp_debug_img_connect", "khp_denoise_params_defaults",
+            "khp_denoise", "khp_denoise_host"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
 ABI_VERSION = 17
@@ -255,6 +279,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_build_accel": (c_int, [c_void_p]),
         "khp_render": (c_int, [c_void_p, P(RenderParams), c_void_p]),
         "khp_render_aov": (c_int, [c_void_p, P(RenderParams), P(AovBuffers)]),
+        "khp_denoise_params_defaults": (None, [P(DenoiseParams)]),
+        "khp_denoise": (c_int, [c_void_p, P(DenoiseParams), c_void_p, P(AovBuffers), c_void_p]),
+        "khp_denoise_host": (c_int, [P(DenoiseParams), c_void_p, P(AovBuffers), c_void_p]),
         "khp_sync": (c_int, [c_void_p]),
         "khp_ctx_params_defaults": (None, [P(CtxParams)]),
         "khp_set_params": (c_int, [c_void_p, P(CtxParams)]),

@@ -276,6 +276,37 @@ class HipContext:
         N.check(self.lib, self.lib.khp_render_aov(self.ptr, ctypes.byref(p), ctypes.byref(buf)), "khp_render_aov")
         return res
 
+    def denoise(self, width, height, guides: dict, colour=None, out=None, device: bool = False, **params):
+        """khp_denoise: the guided a-trous filter of an (H, W, 3) float32 frame
+        over the planes render_aov returns.  `guides` is that dict (missing planes are NULL: a
+        term whose sigma is > 0 needs its plane); `colour` is the frame, or None for the
+        context's framebuffer (read, never written); `out` receives the result (may be
+        `colour`), a new array if None.  device=True: guides, colour and out are DeviceBuffers
+        of this context (out is then required).  **params: khp_denoise_params fields over
+        khp_denoise_params_defaults (iterations, sigma_*, clamp, flags; demodulate=True sets
+        KHP_DENOISE_DEMODULATE).  Returns out."""
+        p, buf, keep = _denoise_args(width, height, guides, device, params)
+        if device:
+            for name, b in (("colour", colour), ("out", out)):
+                if b is not None and not isinstance(b, DeviceBuffer):
+                    raise ValueError(f"{name}: a DeviceBuffer is needed with device=True")
+                if b is not None and b.nbytes < 12 * width * height:
+                    raise ValueError(f"{name}: a DeviceBuffer of {12 * width * height} bytes is needed")
+            if out is None:
+                raise ValueError("out: a DeviceBuffer is needed with device=True")
+            cptr, optr = (colour.ptr if colour is not None else None), out.ptr
+        else:
+            if colour is not None:
+                _frame_check("colour", colour, width, height)
+            if out is None:
+                out = np.zeros((height, width, 3), np.float32)
+            _frame_check("out", out, width, height)
+            cptr = colour.ctypes.data_as(ctypes.c_void_p) if colour is not None else None
+            optr = out.ctypes.data_as(ctypes.c_void_p)
+        N.check(self.lib, self.lib.khp_denoise(self.ptr, ctypes.byref(p), cptr, ctypes.byref(buf), optr), "khp_denoise")
+        del keep
+        return out
+
     def sync(self):
         """khp_sync: complete every asynchronous frame; stats() then sums them."""
         N.check(self.lib, self.lib.khp_sync(self.ptr), "khp_sync")
@@ -541,6 +572,62 @@ class HipContext:
     def gather_framebuffer(self, width, height, spp, depth, tile_size, nranks, rank, root=0):
         p = N.RenderParams(width, height, spp, depth, 0, 0, tile_size, rank, nranks, 0)
         N.check(self.lib, self.lib.khp_gather_framebuffer(self.ptr, ctypes.byref(p), root), "khp_gather_framebuffer")
+
+
+def _frame_check(name, a, width, height):
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.shape != (height, width, 3) or \
+            not a.flags.c_contiguous:
+        raise ValueError(f"{name}: a C-contiguous float32 array of shape {(height, width, 3)} is needed")
+
+
+def _denoise_args(width, height, guides, device, params):
+    """khp_denoise_params and khp_aov_buffers of a denoise call, the planes checked first (dtype,
+    shape, or DeviceBuffer size) as render_aov checks its arrays."""
+    params = dict(params)
+    flags = int(params.pop("flags", 0)) | (N.DENOISE_DEMODULATE if params.pop("demodulate", False) else 0) | \
+        (N.DENOISE_DEVICE if device else 0)
+    for k in params:
+        if k not in dict(N.DenoiseParams._fields_) or k in ("reserved", "width", "height"):
+            raise ValueError(f"khp_denoise_params has no field {k!r} to set")
+    buf, keep = N.AovBuffers(), []
+    for ch, a in guides.items():
+        if ch == "light_ended":     # the restatement's bookkeeping, not a plane
+            continue
+        if ch not in N.AOV_CHANNELS:
+            raise ValueError(f"guides: no channel {ch!r} (one of {', '.join(N.AOV_CHANNELS)})")
+        if a is None or ch == "object":   # the object plane is ignored by the filter
+            continue
+        tail, dtype = N.AOV_CHANNELS[ch]
+        if device:
+            need = int(np.prod((height, width) + tail)) * 4
+            if not isinstance(a, DeviceBuffer) or a.nbytes < need:
+                raise ValueError(f"channel {ch}: a DeviceBuffer of {need} bytes is needed with device=True")
+            ptr = a.ptr
+        else:
+            if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != (height, width) + tail or \
+                    not a.flags.c_contiguous:
+                raise ValueError(f"channel {ch}: a C-contiguous {np.dtype(dtype).name} array of shape "
+                                 f"{(height, width) + tail} is needed")
+            ptr = a.ctypes.data
+        setattr(buf, ch, ctypes.cast(ptr, ctypes.POINTER(ctypes.c_float)))
+        keep.append(a)
+    p = N.DenoiseParams.defaults(width=width, height=height, flags=flags, **params)
+    return p, buf, keep
+
+
+def denoise_host(width, height, guides: dict, colour: np.ndarray, out: np.ndarray | None = None, **params) -> np.ndarray:
+    """khp_denoise_host: HipContext.denoise's filter as a plain host loop over the same per-pixel
+    functions -- no device, no context, the same bits.  numpy arrays only; returns out."""
+    p, buf, keep = _denoise_args(width, height, guides, False, params)
+    _frame_check("colour", colour, width, height)
+    if out is None:
+        out = np.zeros((height, width, 3), np.float32)
+    _frame_check("out", out, width, height)
+    lib = N.load_library()
+    N.check(lib, lib.khp_denoise_host(ctypes.byref(p), colour.ctypes.data_as(ctypes.c_void_p), ctypes.byref(buf),
+                                      out.ctypes.data_as(ctypes.c_void_p)), "khp_denoise_host")
+    del keep
+    return out
 
 
 def comm_init_local(ctxs) -> None:

@@ -426,6 +426,62 @@ typedef struct {
 } khp_aov_buffers;
 khp_status khp_render_aov(khp_ctx* ctx, const khp_render_params* p, const khp_aov_buffers* out);
 
+/* ---- guided a-trous denoiser over the feature buffers -------------------------
+ * An edge-stopping a-trous wavelet filter (B3 spline taps h = {1/16, 1/4, 3/8,
+ * 1/4, 1/16}, 5 x 5 per iteration, iteration i at step 1 << i) of an [H][W][3]
+ * colour frame, guided by the planes khp_render_aov writes (full frames,
+ * premultiplied by coverage; only read; object is ignored).  The result is one
+ * float32 function of the arguments in a fixed order of operations, the same
+ * bits from khp_denoise (gfx950 kernels) and khp_denoise_host (a plain host
+ * loop): no atomics, nothing contracted.  The definition, operation by
+ * operation, is DESIGN.md §13; in short
+ *   prepare  per pixel: cv = coverage, n / t = normal / tangent divided by cv and
+ *            normalised (0 where that has no length), d = depth / cv, c = colour,
+ *            channels above `clamp` set to it, and with DEMODULATE c / m where
+ *            m = max(albedo + (1 - cv), 1e-3) per channel;
+ *   iterate  w = h[dy] h[dx] k_expf(-X) over the taps inside the image whose colour
+ *            is finite, X the sum of the enabled squared distances (colour, normal,
+ *            tangent, depth, coverage) each times 1 / sigma^2; the new colour is
+ *            sum(w c_q) / sum(w) over the taps with w > 0, or the old one if none;
+ *   finish   with DEMODULATE c * m.
+ * A pixel that is not finite takes no part as a tap, has its colour term off and
+ * is replaced by its neighbours' guided mean: it never spreads, and survives only
+ * where no tap counts.  A sigma of 0 turns its term off; a plane whose term is
+ * off is not read and may be NULL (coverage is also read whenever normal,
+ * tangent, depth or albedo is).
+ *
+ * colour and out are [H][W][3] floats, out == colour is allowed.  khp_denoise
+ * with colour == NULL filters the context's framebuffer (the running mean
+ * khp_read_framebuffer returns; width and height must be its size): it completes
+ * asynchronous frames as that call does, reads the framebuffer and writes
+ * nothing of the context.  With a caller's colour the call touches no context
+ * state (own scratch, queued on the context's stream, returns when out is
+ * written), like khp_render_aov.  Whole frames only: a tile rank filters after
+ * khp_gather_framebuffer.
+ *
+ * KHP_EINVAL (checked before the context is touched, khp_last_error names the
+ * cause): a null p, guides, out or ctx; colour == NULL or KHP_DENOISE_DEVICE at
+ * the host entry; width * height == 0 or above 2^31; iterations outside 1..8;
+ * an unknown flag; reserved != 0; a sigma or clamp negative or not finite; a
+ * term on whose plane is NULL; DEMODULATE without albedo; coverage NULL while
+ * normal, tangent, depth or albedo is used.  KHP_ENOTREADY: colour == NULL
+ * before any render.  KIRK has no counterpart. */
+#define KHP_DENOISE_DEVICE     (1u << 0)  /* colour, the guide planes and out are device memory of ctx's GPU */
+#define KHP_DENOISE_DEMODULATE (1u << 1)  /* filter colour / effective albedo, multiply back at the end     */
+typedef struct {
+    uint32_t width, height;
+    uint32_t iterations;        /* 1..8; iteration i uses step 1 << i */
+    uint32_t flags;             /* KHP_DENOISE_* */
+    float sigma_color, sigma_normal, sigma_tangent, sigma_depth, sigma_coverage;  /* 0: the term is off */
+    float clamp;                /* > 0: colour channels above it are set to it first; 0: off */
+    uint32_t reserved[2];       /* 0 */
+} khp_denoise_params;           /* 48 bytes */
+void khp_denoise_params_defaults(khp_denoise_params* out);  /* 0 x 0, 5 iterations, flags 0, 4, 0.35, 0.35, 0.05, 0.25, clamp 0 */
+khp_status khp_denoise(khp_ctx* ctx, const khp_denoise_params* p, const float* colour,
+                       const khp_aov_buffers* guides, float* out);
+khp_status khp_denoise_host(const khp_denoise_params* p, const float* colour,
+                            const khp_aov_buffers* guides, float* out);   /* no device, no context */
+
 /* ABI 7: the light-path (bidirectional) variant of KIRK's GLSL path tracer,
  * lbb_construction.compute:195-403 builds light subpaths
  * (generatePrimaryLightRays / traceLightRays / shadeLightRays) and

@@ -199,6 +199,18 @@ class Context {
     void render_aov(const khp_render_params& p, const khp_aov_buffers& out) {
         check(khp_render_aov(c_, &p, &out), "khp_render_aov");
     }
+    // The guided a-trous filter over those buffers (khp_denoise): colour == nullptr filters the
+    // context's framebuffer (read only); out may be colour.  p from denoise_defaults(w, h).
+    static khp_denoise_params denoise_defaults(uint32_t width, uint32_t height) {
+        khp_denoise_params p;
+        khp_denoise_params_defaults(&p);
+        p.width = width;
+        p.height = height;
+        return p;
+    }
+    void denoise(const khp_denoise_params& p, const float* colour, const khp_aov_buffers& guides, float* out) {
+        check(khp_denoise(c_, &p, colour, &guides, out), "khp_denoise");
+    }
     // KHP_RENDER_ASYNC renders are complete (and accumulated in call order) after sync()
     void sync() { check(khp_sync(c_), "khp_sync"); }
     void read_framebuffer(float* out_rgb) { check(khp_read_framebuffer(c_, out_rgb), "khp_read_framebuffer"); }
