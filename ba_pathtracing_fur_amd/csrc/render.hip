@@ -30,6 +30,7 @@
 #include "device.h"
 #include "device_build.h"
 #include "lightpath.h"
+#include "moments.h"
 
 using namespace khp;
 
@@ -2837,6 +2838,10 @@ struct khp_ctx {
     NextCall series;   // the last synchronous single-pass call, first_sample advanced by its spp
     std::shared_ptr<struct AovState> aov;   // khp_render_aov's own scratch (aov.h), made by its first call
     std::shared_ptr<struct DnState> dn;     // khp_denoise's own scratch (denoise_dev.h), made by its first call
+    // khp_set_moments (moments_dev.h): the per-pixel sample moments beside the framebuffer, two MomRec per
+    // image pixel, made and zeroed with it (moments_remake); mom_stage: khp_read_moments' host callers
+    bool moments_on = false;
+    DevMem mom, mom_stage;
 };
 constexpr size_t LG_SLOTS = 64;
 
@@ -2856,6 +2861,26 @@ static bool render_async(const khp_render_params* p) { return (p->flags & KHP_RE
 
 static khp_status drain(khp_ctx* c);
 static void comm_release(khp_ctx* c);
+
+// The accumulate kernels' twins with khp_set_moments on (moments_dev.h, at the end of this file: the
+// kernels above and below keep their place in the code object).
+__global__ __launch_bounds__(256) void k_accumulate_m(Wave Wv, float* fb, uint32_t fr, MomRec* st);
+__global__ __launch_bounds__(ACC_PIX) void k_accumulate_all_m(Wave Wv, float* fb, MomRec* st);
+
+// The accumulate launches: one frame of Wv (k_accumulate), or every fused frame (k_accumulate_all);
+// with khp_set_moments on, the twins that also fold the moments state.
+static void launch_accumulate(khp_ctx* c, hipStream_t s, const Wave& Wv, uint32_t fr) {
+    const dim3 grid((Wv.P + 255) / 256), block(256);
+    if (c->moments_on) hipLaunchKernelGGL(k_accumulate_m, grid, block, 0, s, Wv, c->fb.as<float>(), fr, c->mom.as<MomRec>());
+    else hipLaunchKernelGGL(k_accumulate, grid, block, 0, s, Wv, c->fb.as<float>(), fr);
+}
+static void launch_accumulate_all(khp_ctx* c, hipStream_t s, const Wave& Wv) {
+    const dim3 grid((Wv.P + ACC_PIX - 1) / ACC_PIX), block(ACC_PIX);
+    const size_t lds = ACC_PIX * (Wv.n_samples + 1) * sizeof(float4);
+    if (c->moments_on) hipLaunchKernelGGL(k_accumulate_all_m, grid, block, lds, s, Wv, c->fb.as<float>(), c->mom.as<MomRec>());
+    else hipLaunchKernelGGL(k_accumulate_all, grid, block, lds, s, Wv, c->fb.as<float>());
+}
+static khp_status moments_remake(khp_ctx* c, size_t npix);   // moments_dev.h
 
 // ---- bounded device waits (ABI 11) ------------------------------------------------------------
 // Without a communicator a wait blocks (hipEventSynchronize / hipStreamSynchronize).
@@ -3899,7 +3924,7 @@ static khp_status wave_ahead_hit(khp_ctx* c, const khp_render_params* p, float* 
     hipEvent_t e0 = next_event(c), e1 = next_event(c);
     (void)hipEventRecord(e0, c->stream);
     if (c->fb_evt) HIPCHK(hipStreamWaitEvent(c->stream, c->fb_evt, 0));
-    hipLaunchKernelGGL(k_accumulate, dim3((P + 255) / 256), dim3(256), 0, c->stream, wa.Wv, c->fb.as<float>(), wa.used);
+    launch_accumulate(c, c->stream, wa.Wv, wa.used);
     HIPCHK(hipGetLastError());
     (void)hipEventRecord(e1, c->stream);
     ++wa.used;
@@ -4287,13 +4312,11 @@ static khp_status enqueue_accumulate(khp_ctx* c, const BatchPlan& pl, const std:
                                      BatchTarget& B) {
     const Wave& Wv = B.Wv;
     const hipStream_t sA = B.sA;
-    const uint32_t P = Wv.P, ns = Wv.n_samples;
     timed(c, B.f, T_OTHER, true, sA);
-    if (pl.wa_frames == 1 && pl.only_renders && ns <= ACC_MAX_SAMPLES) {
-        hipLaunchKernelGGL(k_accumulate_all, dim3((P + ACC_PIX - 1) / ACC_PIX), dim3(ACC_PIX),
-                           ACC_PIX * (ns + 1) * sizeof(float4), sA, Wv, c->fb.as<float>());
+    if (pl.wa_frames == 1 && pl.only_renders && Wv.n_samples <= ACC_MAX_SAMPLES) {
+        launch_accumulate_all(c, sA, Wv);
     } else if (!ops) {   // this call's frame (frames rendered ahead through fusion wait for their calls)
-        hipLaunchKernelGGL(k_accumulate, dim3((P + 255) / 256), dim3(256), 0, sA, Wv, c->fb.as<float>(), 0u);
+        launch_accumulate(c, sA, Wv, 0u);
     } else {
         // fused frames in call order; a gather between two of them runs on the
         // context stream after the first's accumulate and before the second's
@@ -4301,7 +4324,7 @@ static khp_status enqueue_accumulate(khp_ctx* c, const BatchPlan& pl, const std:
         uint32_t fr = 0;
         for (const PendingOp& o : *ops) {
             if (o.kind == PendingOp::RENDER) {
-                hipLaunchKernelGGL(k_accumulate, dim3((P + 255) / 256), dim3(256), 0, sA, Wv, c->fb.as<float>(), fr++);
+                launch_accumulate(c, sA, Wv, fr++);
             } else {
                 HIPCHK(mark_stream(B.f, sA, c->fb_evt));
                 KHPCHK(op_now(c, o));   // waits fb_evt, sets fb_evt to its own end
@@ -4424,6 +4447,7 @@ static khp_status open_batch(khp_ctx* c, const khp_render_params* p, float* out_
         HIPCHK(hipMemsetAsync(c->fb.p, 0, npix * 3 * sizeof(float), c->stream));
         HIPCHK(c->pixheavy.ensure(npix));
         HIPCHK(hipMemsetAsync(c->pixheavy.p, 0, npix, c->stream));
+        if (c->moments_on) KHPCHK(moments_remake(c, npix));   // a zeroed state with every new framebuffer
         c->fbW = p->width;
         c->fbH = p->height;
     }
@@ -5723,3 +5747,7 @@ extern "C" khp_status khp_debug_leaf_reuse(khp_ctx* c, unsigned long long* out) 
     return KHP_OK;
 }
 #endif
+
+// The per-pixel sample moments: the accumulate kernels' twins, k_moments_read, khp_set_moments /
+// khp_read_moments.  Last, so that every kernel above keeps its place in the code object.
+#include "moments_dev.h"

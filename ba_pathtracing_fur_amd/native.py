@@ -183,6 +183,25 @@ class DenoiseParams(ctypes.Structure):
         return p
 
 
+MOMENTS_DEVICE = 1 << 0
+
+
+class Moments(ctypes.Structure):
+    """khp_moments (16 bytes): the per-pixel sample moments' switch, off by default."""
+    _fields_ = [("enabled", c_uint32), ("reserved", c_uint32 * 3)]
+
+
+class MomentsBuffers(ctypes.Structure):
+    """khp_moments_buffers (40 bytes): the planes khp_read_moments writes; a null plane is skipped."""
+    _fields_ = [("mean", POINTER(c_float)), ("m2", POINTER(c_float)), ("count", POINTER(c_uint32)),
+                ("bad", POINTER(c_uint32)), ("rel_error", POINTER(c_float))]
+
+
+# khp_moments_buffers' planes in struct order: name -> (trailing shape, dtype)
+MOMENTS_PLANES = {"mean": ((3,), np.float32), "m2": ((3,), np.float32), "count": ((), np.uint32),
+                  "bad": ((), np.uint32), "rel_error": ((), np.float32)}
+
+
 class Tonemap(ctypes.Structure):
     """khp_tonemap: KIRK::Tonemapper's parameters (Utils/Tonemapping.h:22-33)."""
     _fields_ = [("exposure", c_float), ("bias", c_float), ("gamma", c_float), ("contrast", c_float),
@@ -240,7 +259,8 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_debug_bsdf_eval", "khp_debug_light_dir", "khp_debug_light_isect", "khp_hair_lobes_defaults",
             "khp_set_hair_lobes", "khp_get_hair_lobes", "khp_debug_hair_sample", "khp_render_aov",
             "khp_debug_light_paths", "khp_debug_bdpt_connect", "khp_debug_img_connect", "khp_denoise_params_defaults",
-            "khp_denoise", "khp_denoise_host"]
+            "khp_denoise", "khp_denoise_host", "khp_moments_defaults", "khp_set_moments", "khp_get_moments",
+            "khp_read_moments", "khp_moments_fold_host"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
 ABI_VERSION = 17
@@ -282,6 +302,11 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_denoise_params_defaults": (None, [P(DenoiseParams)]),
         "khp_denoise": (c_int, [c_void_p, P(DenoiseParams), c_void_p, P(AovBuffers), c_void_p]),
         "khp_denoise_host": (c_int, [P(DenoiseParams), c_void_p, P(AovBuffers), c_void_p]),
+        "khp_moments_defaults": (None, [P(Moments)]),
+        "khp_set_moments": (c_int, [c_void_p, P(Moments)]),
+        "khp_get_moments": (c_int, [c_void_p, P(Moments)]),
+        "khp_read_moments": (c_int, [c_void_p, c_uint32, P(MomentsBuffers)]),
+        "khp_moments_fold_host": (c_int, [c_uint32, c_uint32, c_uint32, c_void_p, P(MomentsBuffers)]),
         "khp_sync": (c_int, [c_void_p]),
         "khp_ctx_params_defaults": (None, [P(CtxParams)]),
         "khp_set_params": (c_int, [c_void_p, P(CtxParams)]),

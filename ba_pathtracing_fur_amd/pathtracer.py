@@ -307,6 +307,59 @@ class HipContext:
         del keep
         return out
 
+    MOMENTS_PLANES = tuple(N.MOMENTS_PLANES)   # mean, m2, count, bad, rel_error
+
+    def set_moments(self, enabled: bool) -> bool:
+        """khp_set_moments: switch the per-pixel sample moments on or off.  Enabling
+        makes a zeroed state beside the framebuffer, folded by the renders that follow; disabling
+        frees it; the value it already has is a no-op.  Frames and timings with it off are as
+        without it.  Returns the previous value."""
+        old = self.moments()
+        m = N.Moments(1 if enabled else 0)
+        N.check(self.lib, self.lib.khp_set_moments(self.ptr, ctypes.byref(m)), "khp_set_moments")
+        return old
+
+    def moments(self) -> bool:
+        """khp_get_moments: whether the sample moments are on."""
+        m = N.Moments()
+        N.check(self.lib, self.lib.khp_get_moments(self.ptr, ctypes.byref(m)), "khp_get_moments")
+        return bool(m.enabled)
+
+    def read_moments(self, width, height, device: bool = False, planes=MOMENTS_PLANES, out: dict | None = None) -> dict:
+        """khp_read_moments: the `planes` asked for of the moments state as a dict -- mean, m2
+        (H, W, 3) float32: the finite samples' mean and sum of squared deviations; count, bad
+        (H, W) uint32: finite and rejected samples; rel_error (H, W) float32: the relative standard
+        error of the pixel's mean, +inf below two samples.  width and height are the framebuffer's.
+        device=True: the planes are DeviceBuffers of this context (KHP_MOMENTS_DEVICE).  `out`
+        supplies the arrays (or DeviceBuffers) to write into; otherwise they are made here."""
+        planes = tuple(planes)
+        for ch in planes:
+            if ch not in N.MOMENTS_PLANES:
+                raise ValueError(f"khp_read_moments has no plane {ch!r} (one of {', '.join(N.MOMENTS_PLANES)})")
+        res, buf = {}, N.MomentsBuffers()
+        for ch in planes:
+            tail, dtype = N.MOMENTS_PLANES[ch]
+            shape = (height, width) + tail
+            a = out[ch] if out is not None and ch in out else None
+            if device:
+                need = int(np.prod(shape)) * 4
+                if a is None:
+                    a = DeviceBuffer(self, need)
+                if not isinstance(a, DeviceBuffer) or a.nbytes < need:
+                    raise ValueError(f"plane {ch}: a DeviceBuffer of {need} bytes is needed with device=True")
+                ptr = a.ptr
+            else:
+                if a is None:
+                    a = np.zeros(shape, dtype)
+                if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != shape or not a.flags.c_contiguous:
+                    raise ValueError(f"plane {ch}: a C-contiguous {np.dtype(dtype).name} array of shape {shape} is needed")
+                ptr = a.ctypes.data
+            setattr(buf, ch, ctypes.cast(ptr, ctypes.POINTER(ctypes.c_float if dtype == np.float32 else ctypes.c_uint32)))
+            res[ch] = a
+        N.check(self.lib, self.lib.khp_read_moments(self.ptr, N.MOMENTS_DEVICE if device else 0, ctypes.byref(buf)),
+                "khp_read_moments")
+        return res
+
     def sync(self):
         """khp_sync: complete every asynchronous frame; stats() then sums them."""
         N.check(self.lib, self.lib.khp_sync(self.ptr), "khp_sync")
@@ -628,6 +681,41 @@ def denoise_host(width, height, guides: dict, colour: np.ndarray, out: np.ndarra
                                       out.ctypes.data_as(ctypes.c_void_p)), "khp_denoise_host")
     del keep
     return out
+
+
+def moments_fold_host(samples: np.ndarray, first_sample: int = 0, state: dict | None = None) -> dict:
+    """khp_moments_fold_host: the fold of HipContext's sample moments as a plain host loop over the
+    same functions the kernels compile -- no device, no context, the same bits.  `samples` is
+    (K, ..., 3) float32, sample s having global index first_sample + s; `state` is a dict of mean,
+    m2, count and bad to continue from (left as it is), or None for a zeroed one.  Returns the new
+    state with rel_error, the planes shaped like one sample."""
+    s = np.ascontiguousarray(samples, np.float32)
+    if s.ndim < 2 or s.shape[-1] != 3:
+        raise ValueError("samples: a float32 array of shape (K, ..., 3) is needed")
+    shape = s.shape[1:-1]
+    n_pix = int(np.prod(shape, dtype=np.int64))
+    res, buf = {}, N.MomentsBuffers()
+    for ch, (tail, dtype) in N.MOMENTS_PLANES.items():
+        if state is not None and ch != "rel_error":
+            a = np.array(state[ch], dtype, order="C")
+            if a.shape != shape + tail:
+                raise ValueError(f"state[{ch!r}]: shape {shape + tail} is needed")
+        else:
+            a = np.zeros(shape + tail, dtype)
+        setattr(buf, ch, ctypes.cast(a.ctypes.data, ctypes.POINTER(ctypes.c_float if dtype == np.float32 else ctypes.c_uint32)))
+        res[ch] = a
+    lib = N.load_library()
+    N.check(lib, lib.khp_moments_fold_host(n_pix, int(first_sample), s.shape[0], s.ctypes.data_as(ctypes.c_void_p),
+                                           ctypes.byref(buf)), "khp_moments_fold_host")
+    return res
+
+
+def moments_variance(state: dict) -> np.ndarray:
+    """The unbiased sample variance m2 / (n - 1) per channel of a moments state (read_moments or
+    moments_fold_host), NaN where n < 2.  numpy, a convenience only."""
+    n = np.asarray(state["count"]).astype(np.float64)[..., None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(n >= 2, np.asarray(state["m2"], np.float64) / (n - 1), np.nan).astype(np.float32)
 
 
 def comm_init_local(ctxs) -> None:

@@ -482,6 +482,70 @@ khp_status khp_denoise(khp_ctx* ctx, const khp_denoise_params* p, const float* c
 khp_status khp_denoise_host(const khp_denoise_params* p, const float* colour,
                             const khp_aov_buffers* guides, float* out);   /* no device, no context */
 
+/* ---- per-pixel sample moments: robust mean, variance, error plane --------------
+ * An opt-in second accumulator beside the framebuffer.  Per pixel it holds n, the
+ * count of finite samples, their mean, M2, their sum of squared deviations
+ * (Welford), and bad, the count of rejected samples; all zero when made.  It is
+ * folded by the launches that fold the running mean, in the same sample order,
+ * whatever the schedule (synchronous or asynchronous, fused, chunked, rendered
+ * ahead, in flight): the state is a function of the samples alone (no atomics;
+ * DESIGN.md §14).  The fold of a sample colour x with global index k, every step
+ * one float32 operation in the order written, nothing contracted:
+ *   k == 0                    the state is first set to zero (the framebuffer's
+ *                             own restart rule);
+ *   a channel of x not finite bad += 1, nothing else;
+ *   otherwise                 n += 1, nf = (float)n;
+ *     n == 1                  mean = x (an assignment: -0 survives), m2 = +0;
+ *     n > 1, per channel      d = x - mean; mean = mean + d / nf; e = x - mean;
+ *                             m2 = m2 + d * e.
+ * For a series from sample 0 with no rejected sample, mean goes through the
+ * running mean's own operations: it equals the framebuffer bit for bit on every
+ * pixel with bad == 0; where bad > 0 the framebuffer is not finite and mean is.
+ * Finite but huge samples can overflow m2 to +inf or NaN; nothing is clamped.
+ * The error plane is computed on read: s = (m2.r + m2.g) + m2.b, mu = (mean.r +
+ * mean.g) + mean.b, rel_error = +inf where n < 2, else
+ * sqrtf(s / (nf * (nf - 1.0f))) / (fabsf(mu) + 1e-3f): the relative standard
+ * error of the pixel's mean with the channels summed.
+ *
+ * Off by default, and with it off nothing changes.  khp_set_moments completes
+ * frames in flight first.  Enabling makes a zeroed state, allocated with the
+ * framebuffer (at once if there is one) and made anew, zeroed, whenever the
+ * framebuffer is (a size change); enabled in mid-series it counts only the
+ * samples folded since.  Disabling frees it; setting the value it has is a
+ * no-op.  KHP_EINVAL: a null argument, enabled > 1, reserved != 0.
+ *
+ * khp_read_moments completes asynchronous frames as khp_read_framebuffer does,
+ * writes the non-NULL planes and changes nothing of the context.  KHP_EINVAL
+ * (checked before the context is touched): a null ctx or out, every plane NULL,
+ * an unknown flag; with KHP_MOMENTS_DEVICE a plane that is not device memory.
+ * KHP_ENOTREADY: moments off, or nothing rendered yet.  Pixels of tiles this rank
+ * does not own are never folded and read as zeros (count 0, rel_error +inf); a
+ * host assembles ranks by khp_gather_plan.
+ *
+ * khp_moments_fold_host is the definition as a plain host loop over the same
+ * functions the kernels compile: samples is [n_samples][n_pixels][3], sample s
+ * has global index first_sample + s, the state planes mean, m2, count and bad are
+ * read and written, rel_error (or NULL) is written at the end.  KHP_EINVAL: a
+ * null argument or state plane other than rel_error, n_pixels == 0, first_sample +
+ * n_samples overflowing.  n_samples == 0 only writes rel_error.  KIRK has no
+ * counterpart. */
+typedef struct { uint32_t enabled; uint32_t reserved[3]; } khp_moments;      /* 16 bytes; reserved 0 */
+void       khp_moments_defaults(khp_moments* out);                          /* off */
+khp_status khp_set_moments(khp_ctx* ctx, const khp_moments* m);
+khp_status khp_get_moments(khp_ctx* ctx, khp_moments* out);
+
+#define KHP_MOMENTS_DEVICE (1u << 0)     /* every pointer is device memory of ctx's GPU */
+typedef struct {
+    float*    mean;       /* [H][W][3] or NULL */
+    float*    m2;         /* [H][W][3] or NULL */
+    uint32_t* count;      /* [H][W]    or NULL */
+    uint32_t* bad;        /* [H][W]    or NULL */
+    float*    rel_error;  /* [H][W]    or NULL */
+} khp_moments_buffers;
+khp_status khp_read_moments(khp_ctx* ctx, uint32_t flags, const khp_moments_buffers* out);
+khp_status khp_moments_fold_host(uint32_t n_pixels, uint32_t first_sample, uint32_t n_samples,
+                                 const float* samples, const khp_moments_buffers* state);   /* no device, no context */
+
 /* ABI 7: the light-path (bidirectional) variant of KIRK's GLSL path tracer,
  * lbb_construction.compute:195-403 builds light subpaths
  * (generatePrimaryLightRays / traceLightRays / shadeLightRays) and
