@@ -21,12 +21,12 @@ def set_hw_queues(n: int = 8) -> None:
 
 from . import native  # noqa: E402,F401
 from .native import (AOV_CHANNELS, DENOISE_DEMODULATE, DENOISE_DEVICE, HAIR_LOBE_R, HAIR_LOBE_TRT,  # noqa: E402
-                     HAIR_LOBE_TT, MOMENTS_DEVICE, MOMENTS_PLANES, AovBuffers, DenoiseParams)
-from .pathtracer import (BVH, BsdfFactory, HipContext, PathTracer, ShaderFactory, comm_unique_id,  # noqa: E402
-                         denoise_host, moments_fold_host, moments_variance)
+                     HAIR_LOBE_TT, MOMENTS_DEVICE, MOMENTS_PLANES, AdaptiveParams, AovBuffers, DenoiseParams)
+from .pathtracer import (BVH, BsdfFactory, HipContext, PathTracer, ShaderFactory, adaptive_select_host,  # noqa: E402
+                         comm_unique_id, denoise_host, moments_fold_host, moments_variance)
 from .scenes import SceneData, build_config  # noqa: E402
 
 __all__ = ["set_hw_queues", "native", "BVH", "BsdfFactory", "HipContext", "PathTracer", "ShaderFactory", "SceneData",
            "build_config", "comm_unique_id", "HAIR_LOBE_R", "HAIR_LOBE_TT", "HAIR_LOBE_TRT", "AovBuffers",
            "AOV_CHANNELS", "DenoiseParams", "DENOISE_DEVICE", "DENOISE_DEMODULATE", "denoise_host", "MOMENTS_DEVICE",
-           "MOMENTS_PLANES", "moments_fold_host", "moments_variance"]
+           "MOMENTS_PLANES", "moments_fold_host", "moments_variance", "AdaptiveParams", "adaptive_select_host"]

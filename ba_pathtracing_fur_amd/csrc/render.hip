@@ -2842,6 +2842,7 @@ struct khp_ctx {
     // image pixel, made and zeroed with it (moments_remake); mom_stage: khp_read_moments' host callers
     bool moments_on = false;
     DevMem mom, mom_stage;
+    std::shared_ptr<struct AdaptState> ad;  // khp_render_adaptive's own scratch (adaptive_dev.h), made by its first call
 };
 constexpr size_t LG_SLOTS = 64;
 
@@ -2881,6 +2882,16 @@ static void launch_accumulate_all(khp_ctx* c, hipStream_t s, const Wave& Wv) {
     else hipLaunchKernelGGL(k_accumulate_all, grid, block, lds, s, Wv, c->fb.as<float>());
 }
 static khp_status moments_remake(khp_ctx* c, size_t npix);   // moments_dev.h
+
+// khp_render_adaptive (adaptive_dev.h, at the end of this file too): an adaptive batch folds with
+// k_accumulate_a, and its pixel view -- the active pixels among the owned ones -- comes from adaptive_list.
+__global__ __launch_bounds__(256) void k_accumulate_a(Wave Wv, float* fb, uint32_t fr, MomRec* st);
+struct AdaptPass {
+    const khp_adaptive_params* prm;
+    khp_adaptive_result* res;   // nullable
+};
+static khp_status adaptive_list(khp_ctx* c, const khp_render_params* p, const AdaptPass& ad, const uint32_t** pix,
+                                uint32_t* n);
 
 // ---- bounded device waits (ABI 11) ------------------------------------------------------------
 // Without a communicator a wait blocks (hipEventSynchronize / hipStreamSynchronize).
@@ -3954,6 +3965,10 @@ struct BatchOpening {
     bool geometry_change = false;  // new framebuffer or pixel list: the batch forks from the context stream
     bool served = false;           // the pass was rendered ahead and is accumulated (wave_ahead_hit): nothing to enqueue
     int slot = 0;                  // the frame slot (its path set and streams)
+    // the batch's pixel view: the owned list (c->pix), or an adaptive pass's active pixels among them
+    const uint32_t* pix = nullptr;
+    uint32_t n_pix = 0;
+    bool adaptive = false;
 };
 // Every decision enqueue_frames makes before it enqueues anything (plan_batch); the stages read them here.
 struct BatchPlan {
@@ -3961,7 +3976,9 @@ struct BatchPlan {
     std::vector<uint32_t> fs0;   // fused frames: their first samples, in call order
     uint32_t nf, wa_frames;      // fs0.size(); of them this call's pass + those rendered ahead through fusion (1: off)
     bool only_renders;           // no gather or snapshot among the batch's operations
-    uint32_t P_all, P_chunk, S_chunk;   // owned pixels; pixels and samples per chunk
+    uint32_t P_all, P_chunk, S_chunk;   // the pixel view's pixels; pixels and samples per chunk
+    const uint32_t* pix;         // the pixel view (device): the owned list, or an adaptive pass's active list
+    bool adaptive;               // khp_render_adaptive: folded by k_accumulate_a, nothing rendered ahead
     size_t call_paths;           // P_all x spp x nf
     bool bdm;                    // the light-path variant, with sh_per_path connection records per path
     uint32_t sh_per_path;
@@ -3995,7 +4012,9 @@ static khp_status plan_batch(khp_ctx* c, const khp_render_params* p, const std::
         for (const PendingOp& op : *ops)
             if (op.kind == PendingOp::RENDER) pl.fs0.push_back(op.p.first_sample);
     pl.only_renders = !ops || pl.fs0.size() == ops->size();
-    const uint32_t P_all = pl.P_all = (uint32_t)c->pix_host.size();
+    const uint32_t P_all = pl.P_all = o.n_pix;
+    pl.pix = o.pix;
+    pl.adaptive = o.adaptive;
     // each persistent launch of a batch in flight takes 1/F of the resident grid
     const int G = pl.async ? frames_in_flight(c) : 1;
     pl.grid_ext = std::max(1, c->grid_ext / G), pl.grid_sh = std::max(1, c->grid_sh / G);
@@ -4084,7 +4103,7 @@ static khp_status plan_batch(khp_ctx* c, const khp_render_params* p, const std::
     // context stream so the per-bounce snapshots are exact.
     pl.overlap = !pl.stats && !c->prm.serial_stages;
     // render-ahead (khp_ctx_params.render_ahead): synchronous path-kernel calls of one chunk
-    pl.ahead = pl.use_path && !pl.async && !ops && nf == 1 && c->prm.render_ahead != 0 && P_all > 0 &&
+    pl.ahead = pl.use_path && !pl.async && !ops && !pl.adaptive && nf == 1 && c->prm.render_ahead != 0 && P_all > 0 &&
                P_chunk >= P_all && S_chunk >= p->spp && pl.call_paths <= (size_t)PID_MASK + 1;
     // ray sorting from bounce rs_from (0: off); not with hit sorting, the light-path
     // variant or queue dumps, which read the queues in their own order.  Automatic
@@ -4313,7 +4332,10 @@ static khp_status enqueue_accumulate(khp_ctx* c, const BatchPlan& pl, const std:
     const Wave& Wv = B.Wv;
     const hipStream_t sA = B.sA;
     timed(c, B.f, T_OTHER, true, sA);
-    if (pl.wa_frames == 1 && pl.only_renders && Wv.n_samples <= ACC_MAX_SAMPLES) {
+    if (pl.adaptive) {   // the moments fold alone, the framebuffer pixel from its mean (adaptive_dev.h)
+        hipLaunchKernelGGL(k_accumulate_a, dim3((Wv.P + 255) / 256), dim3(256), 0, sA, Wv, c->fb.as<float>(), 0u,
+                           c->mom.as<MomRec>());
+    } else if (pl.wa_frames == 1 && pl.only_renders && Wv.n_samples <= ACC_MAX_SAMPLES) {
         launch_accumulate_all(c, sA, Wv);
     } else if (!ops) {   // this call's frame (frames rendered ahead through fusion wait for their calls)
         launch_accumulate(c, sA, Wv, 0u);
@@ -4473,10 +4495,16 @@ static khp_status open_batch(khp_ctx* c, const khp_render_params* p, float* out_
 // render operations, which differ only in first_sample, and the framebuffer
 // gathers between them, in call order; p = the first render's parameters).
 static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* out_rgb,
-                                 const std::vector<PendingOp>* ops) {
+                                 const std::vector<PendingOp>* ops, const AdaptPass* ad = nullptr) {
     BatchOpening o;
     KHPCHK(open_batch(c, p, out_rgb, !ops, o));
     if (o.served) return KHP_OK;
+    o.pix = c->pix.as<uint32_t>();
+    o.n_pix = (uint32_t)c->pix_host.size();
+    if (ad) {   // khp_render_adaptive: the active pixels among them, chosen on the device; the count comes back here
+        KHPCHK(adaptive_list(c, p, *ad, &o.pix, &o.n_pix));
+        o.adaptive = true;
+    }
     BatchPlan pl;
     KHPCHK(plan_batch(c, p, ops, o, pl));
     FrameSlot& f = c->fs[o.slot];
@@ -4504,7 +4532,7 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
     if (sB != sA) KHPCHK(order_after(f, sA, sB));
     Wave& Wv = B.Wv = wave_view(c, w);
     if (pl.ahead) KHPCHK(ahead_prepare(c, p, pl.call_paths, sA, B.AH, &Wv.CK));
-    Wv.pix = c->pix.as<uint32_t>();
+    Wv.pix = pl.pix;
     Wv.W = p->width;
     Wv.H = p->height;
     Wv.seed = p->seed;
@@ -4515,7 +4543,7 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
         HIPCHK(w.pixo.ensure((size_t)pl.P_all * sizeof(uint32_t)));
         HIPCHK(w.pixcnt.ensure(2 * sizeof(uint32_t)));
         HIPCHK(hipMemsetAsync(w.pixcnt.p, 0, 2 * sizeof(uint32_t), sA));
-        hipLaunchKernelGGL(k_pix_order, dim3((pl.P_all + 255) / 256), dim3(256), 0, sA, c->pix.as<uint32_t>(), pl.P_all,
+        hipLaunchKernelGGL(k_pix_order, dim3((pl.P_all + 255) / 256), dim3(256), 0, sA, pl.pix, pl.P_all,
                            c->pixheavy.as<uint8_t>(), w.pixo.as<uint32_t>(), w.pixcnt.as<uint32_t>());
         Wv.pix = w.pixo.as<uint32_t>();
         Wv.pixheavy = c->pixheavy.as<uint8_t>();
@@ -4564,7 +4592,7 @@ static khp_status enqueue_frames(khp_ctx* c, const khp_render_params* p, float* 
         c->ra.counted = false;
     }
     c->report_open = false;
-    if (pl.sync1) expect_successor(c->series, c, *p);
+    if (pl.sync1 && !pl.adaptive) expect_successor(c->series, c, *p);
     return KHP_OK;
 }
 
@@ -5751,3 +5779,4 @@ extern "C" khp_status khp_debug_leaf_reuse(khp_ctx* c, unsigned long long* out) 
 // The per-pixel sample moments: the accumulate kernels' twins, k_moments_read, khp_set_moments /
 // khp_read_moments.  Last, so that every kernel above keeps its place in the code object.
 #include "moments_dev.h"
+#include "adaptive_dev.h"   // khp_render_adaptive: passes over the unconverged pixels only

@@ -202,6 +202,27 @@ MOMENTS_PLANES = {"mean": ((3,), np.float32), "m2": ((3,), np.float32), "count":
                   "bad": ((), np.uint32), "rel_error": ((), np.float32)}
 
 
+class AdaptiveParams(ctypes.Structure):
+    """khp_adaptive_params (16 bytes): an adaptive pass's convergence bound and sample limits."""
+    _fields_ = [("threshold", c_float), ("min_samples", c_uint32), ("max_samples", c_uint32), ("reserved", c_uint32)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "AdaptiveParams":
+        """khp_adaptive_defaults (threshold 0.05, min_samples 8, no cap) with fields changed."""
+        p = cls()
+        load_library().khp_adaptive_defaults(ctypes.byref(p))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise AttributeError(f"khp_adaptive_params has no field {k}")
+            setattr(p, k, v)
+        return p
+
+
+class AdaptiveResult(ctypes.Structure):
+    """khp_adaptive_result (32 bytes): the rank's pixel count and the pass's active pixels."""
+    _fields_ = [("owned", c_uint64), ("active", c_uint64), ("reserved", c_uint64 * 2)]
+
+
 class Tonemap(ctypes.Structure):
     """khp_tonemap: KIRK::Tonemapper's parameters (Utils/Tonemapping.h:22-33)."""
     _fields_ = [("exposure", c_float), ("bias", c_float), ("gamma", c_float), ("contrast", c_float),
@@ -260,7 +281,8 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_set_hair_lobes", "khp_get_hair_lobes", "khp_debug_hair_sample", "khp_render_aov",
             "khp_debug_light_paths", "khp_debug_bdpt_connect", "khp_debug_img_connect", "khp_denoise_params_defaults",
             "khp_denoise", "khp_denoise_host", "khp_moments_defaults", "khp_set_moments", "khp_get_moments",
-            "khp_read_moments", "khp_moments_fold_host"]
+            "khp_read_moments", "khp_moments_fold_host", "khp_adaptive_defaults", "khp_render_adaptive",
+            "khp_adaptive_select_host", "khp_debug_adaptive_select", "khp_debug_adaptive_list"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
 ABI_VERSION = 17
@@ -307,6 +329,13 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_get_moments": (c_int, [c_void_p, P(Moments)]),
         "khp_read_moments": (c_int, [c_void_p, c_uint32, P(MomentsBuffers)]),
         "khp_moments_fold_host": (c_int, [c_uint32, c_uint32, c_uint32, c_void_p, P(MomentsBuffers)]),
+        "khp_adaptive_defaults": (None, [P(AdaptiveParams)]),
+        "khp_render_adaptive": (c_int, [c_void_p, P(RenderParams), P(AdaptiveParams), P(AdaptiveResult), c_void_p]),
+        "khp_adaptive_select_host": (c_int, [P(AdaptiveParams), c_uint32, P(MomentsBuffers), c_uint32, P(c_uint32),
+                                             P(c_uint32), P(c_uint32)]),
+        "khp_debug_adaptive_select": (c_int, [c_void_p, P(AdaptiveParams), c_uint32, c_uint32, P(MomentsBuffers),
+                                              c_uint32, P(c_uint32), P(c_uint32), P(c_uint32)]),
+        "khp_debug_adaptive_list": (c_int, [c_void_p, P(c_uint32), P(c_uint32), P(c_double)]),
         "khp_sync": (c_int, [c_void_p]),
         "khp_ctx_params_defaults": (None, [P(CtxParams)]),
         "khp_set_params": (c_int, [c_void_p, P(CtxParams)]),

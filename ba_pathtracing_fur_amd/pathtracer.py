@@ -360,6 +360,77 @@ class HipContext:
                 "khp_read_moments")
         return res
 
+    def render_adaptive(self, width, height, spp, depth, seed=0x4B49524B, first_sample=0, threshold=None,
+                        min_samples=None, max_samples=None, tile_size=64, tile_rank=0, tile_nranks=1, out=None,
+                        readback=True):
+        """khp_render_adaptive: samples first_sample .. first_sample + spp - 1 of the
+        ACTIVE pixels only -- those whose rel_error (read_moments) is still above `threshold`, or that
+        have fewer than `min_samples` samples, and fewer than `max_samples` (0: no cap); every owned
+        pixel when first_sample == 0.  set_moments(True) first.  The moments are folded as render()
+        folds them and the framebuffer takes `mean` on the active pixels; the others keep state and
+        framebuffer.  Parameters left None are khp_adaptive_defaults' (0.05, 8, 0).  `out`: an
+        (H, W, 3) float32 array, or a DeviceBuffer of this context (KHP_RENDER_OUT_DEVICE).  Returns
+        (frame or None, {"owned": the rank's pixels, "active": those traced})."""
+        a = _adaptive_params(threshold, min_samples, max_samples)
+        flags = 0 if readback else N.RENDER_NO_READBACK
+        ptr = None
+        if readback and isinstance(out, DeviceBuffer):
+            if out.nbytes < 12 * width * height:
+                raise ValueError(f"out: a DeviceBuffer of {12 * width * height} bytes is needed")
+            flags |= N.RENDER_OUT_DEVICE
+            ptr = out.ptr
+        elif readback:
+            if out is None:
+                out = np.zeros((height, width, 3), np.float32)
+            _frame_check("out", out, width, height)
+            ptr = out.ctypes.data_as(ctypes.c_void_p)
+        p = N.RenderParams(width, height, spp, depth, seed, first_sample, tile_size, tile_rank, tile_nranks, flags)
+        res = N.AdaptiveResult()
+        N.check(self.lib, self.lib.khp_render_adaptive(self.ptr, ctypes.byref(p), ctypes.byref(a), ctypes.byref(res), ptr),
+                "khp_render_adaptive")
+        return (out if readback else None), {"owned": int(res.owned), "active": int(res.active)}
+
+    def render_to_error(self, width, height, spp, depth, threshold, max_passes, seed=0x4B49524B, min_samples=None,
+                        max_samples=None, tile_size=64, tile_rank=0, tile_nranks=1) -> list:
+        """Adaptive passes of `spp` samples from sample 0 until no pixel is active or `max_passes`
+        passes ran (nothing is read back; read_framebuffer and read_moments afterwards).  Returns the
+        active count of every pass run, the first being every owned pixel."""
+        counts = []
+        for k in range(int(max_passes)):
+            _f, res = self.render_adaptive(width, height, spp, depth, seed=seed, first_sample=k * spp,
+                                           threshold=threshold, min_samples=min_samples, max_samples=max_samples,
+                                           tile_size=tile_size, tile_rank=tile_rank, tile_nranks=tile_nranks,
+                                           readback=False)
+            counts.append(res["active"])
+            if res["active"] == 0:
+                break
+        return counts
+
+    def debug_adaptive_select(self, state: dict, owned, first_sample: int, **params) -> np.ndarray:
+        """khp_debug_adaptive_select: the selection kernels of render_adaptive alone, over a caller's
+        state (mean, m2, count, bad by pixel) and owned list, in scratch of their own: the active
+        pixels, in owned order.  **params: threshold, min_samples, max_samples."""
+        a = _adaptive_params(**params)
+        buf, own, n_pix, keep = _select_args(state, owned)
+        act = np.empty(max(1, own.size), np.uint32)
+        n = ctypes.c_uint32()
+        N.check(self.lib, self.lib.khp_debug_adaptive_select(self.ptr, ctypes.byref(a), int(first_sample), n_pix,
+                                                             ctypes.byref(buf), own.size, N.uptr(own), N.uptr(act),
+                                                             ctypes.byref(n)), "khp_debug_adaptive_select")
+        del keep
+        return act[:n.value].copy()
+
+    def debug_adaptive_list(self, timing: bool = False):
+        """khp_debug_adaptive_list: the last adaptive pass's active pixels, in owned order; with
+        timing=True, (pixels, the device milliseconds of that pass's selection)."""
+        n, ms = ctypes.c_uint32(), ctypes.c_double()
+        N.check(self.lib, self.lib.khp_debug_adaptive_list(self.ptr, ctypes.byref(n), None, None),
+                "khp_debug_adaptive_list")
+        pix = np.empty(max(1, n.value), np.uint32)
+        N.check(self.lib, self.lib.khp_debug_adaptive_list(self.ptr, ctypes.byref(n), N.uptr(pix), ctypes.byref(ms)),
+                "khp_debug_adaptive_list")
+        return (pix[:n.value].copy(), ms.value) if timing else pix[:n.value].copy()
+
     def sync(self):
         """khp_sync: complete every asynchronous frame; stats() then sums them."""
         N.check(self.lib, self.lib.khp_sync(self.ptr), "khp_sync")
@@ -708,6 +779,44 @@ def moments_fold_host(samples: np.ndarray, first_sample: int = 0, state: dict | 
     N.check(lib, lib.khp_moments_fold_host(n_pix, int(first_sample), s.shape[0], s.ctypes.data_as(ctypes.c_void_p),
                                            ctypes.byref(buf)), "khp_moments_fold_host")
     return res
+
+
+def _adaptive_params(threshold=None, min_samples=None, max_samples=None) -> "N.AdaptiveParams":
+    given = {"threshold": threshold, "min_samples": min_samples, "max_samples": max_samples}
+    return N.AdaptiveParams.defaults(**{k: v for k, v in given.items() if v is not None})
+
+
+def _select_args(state: dict, owned):
+    """(khp_moments_buffers over the state's planes flattened by pixel, the owned list, the pixel count, keep-alives)."""
+    buf, keep = N.MomentsBuffers(), []
+    n_pix = int(np.asarray(state["count"]).size)
+    for ch, (tail, dtype) in N.MOMENTS_PLANES.items():
+        if ch == "rel_error":
+            continue
+        a = np.ascontiguousarray(state[ch], dtype).reshape((n_pix,) + tail)
+        setattr(buf, ch, ctypes.cast(a.ctypes.data, ctypes.POINTER(ctypes.c_float if dtype == np.float32 else ctypes.c_uint32)))
+        keep.append(a)
+    own = np.ascontiguousarray(owned, np.uint32).reshape(-1)
+    if own.size and int(own.max()) >= n_pix:
+        raise ValueError(f"owned: a pixel index is not below the state's {n_pix} pixels")
+    keep.append(own)
+    return buf, own, n_pix, keep
+
+
+def adaptive_select_host(state: dict, owned, first_sample: int, **params) -> np.ndarray:
+    """khp_adaptive_select_host: the pixels of `owned` an adaptive pass starting at first_sample
+    traces, in owned order, as a plain host loop over the rule the selection kernel compiles -- no
+    device, no context.  `state`: mean, m2, count and bad by image pixel (read_moments or
+    moments_fold_host).  **params: threshold, min_samples, max_samples over khp_adaptive_defaults."""
+    a = _adaptive_params(**params)
+    buf, own, _n_pix, keep = _select_args(state, owned)
+    act = np.empty(max(1, own.size), np.uint32)
+    n = ctypes.c_uint32()
+    lib = N.load_library()
+    N.check(lib, lib.khp_adaptive_select_host(ctypes.byref(a), int(first_sample), ctypes.byref(buf), own.size,
+                                              N.uptr(own), N.uptr(act), ctypes.byref(n)), "khp_adaptive_select_host")
+    del keep
+    return act[:n.value].copy()
 
 
 def moments_variance(state: dict) -> np.ndarray:

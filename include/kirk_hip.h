@@ -546,6 +546,86 @@ khp_status khp_read_moments(khp_ctx* ctx, uint32_t flags, const khp_moments_buff
 khp_status khp_moments_fold_host(uint32_t n_pixels, uint32_t first_sample, uint32_t n_samples,
                                  const float* samples, const khp_moments_buffers* state);   /* no device, no context */
 
+/* ---- adaptive passes: render the unconverged pixels only -------------------------
+ * khp_render_adaptive renders samples first_sample .. first_sample + spp - 1 for the
+ * ACTIVE pixels of this rank only; the active pixels are chosen on the device from
+ * the moments state (khp_set_moments must be on).
+ *
+ * Selection.  For an owned pixel with records a = (mean, n) and b = (m2, bad), let
+ * t = n + bad.  The pixel is active iff
+ *   first_sample == 0                      (a restart: every owned pixel; the fold's
+ *                                           k == 0 rule zeroes the state), or
+ *   t < min_samples, or
+ *   (max_samples == 0 || t < max_samples) && (n < 2 || !(rel_error <= threshold)),
+ * rel_error being the error plane's value (above) for a and b.  The comparison is
+ * negated on purpose: a NaN error (an overflowed m2) stays active until max_samples
+ * stops it, and so does a pixel below two finite samples, whose error is +inf by
+ * definition, at every threshold, +inf included.  The active list is the owned list
+ * (khp_gather_plan order) with the inactive pixels removed and the order kept: a
+ * deterministic function of the arguments.  khp_adaptive_select_host is the same
+ * rule, compiled from the same function, as a plain host loop: state holds the
+ * planes mean, m2, count and bad by image pixel (rel_error is ignored), owned the
+ * n_owned pixel indices, active has room for n_owned.  KHP_EINVAL: a null argument
+ * (owned and active may be NULL when n_owned == 0), a null state plane, a bad
+ * threshold or reserved.
+ *
+ * Pass.  Every active pixel traces the samples khp_render traces for that pixel and
+ * those sample indices (same keys, rays, bounces), so a sample's colour is
+ * khp_render's bit for bit.  A caller advances first_sample by spp per pass whichever
+ * pixels were active; a pixel's sample set is the union of the passes it was active
+ * in.  spp is added whole: a pixel may end above max_samples by less than spp.
+ *
+ * Fold.  Per active pixel, in increasing k, the moments fold above, unchanged; then
+ * framebuffer[pixel] = mean, a plain store ((0, 0, 0) while n == 0).  The
+ * framebuffer's (k + 1) running mean is not applied: it assumes every pixel has k
+ * samples.  Inactive pixels keep their state and their framebuffer value bit for
+ * bit.  In a series run adaptively from sample 0 the framebuffer therefore equals
+ * mean on every owned pixel and is finite everywhere; khp_read_rgba8, khp_denoise
+ * with colour == NULL and khp_gather_framebuffer work on it as they are.  A later
+ * khp_render pass folds the framebuffer by the global k as always: the moments stay
+ * exact, the framebuffer then holds that arithmetic's result.
+ *
+ * p is as for khp_render; flags is 0, KHP_RENDER_OUT_DEVICE or
+ * KHP_RENDER_NO_READBACK.  The call is synchronous: it completes frames in flight
+ * first, drops every piece of work rendered ahead for another call and leaves none
+ * behind.  A new size makes the framebuffer and a zeroed state.  With no active pixel
+ * nothing is traced or folded, the call is KHP_OK and out_rgb is still delivered.
+ * res (or NULL) receives the rank's pixel count and the active list's length.
+ * KHP_EINVAL (checked before the context is touched, khp_last_error names the
+ * cause): a null ctx, p or a, threshold negative or NaN (+inf is allowed),
+ * reserved != 0, spp == 0 or above 2^24, KHP_RENDER_ASYNC or KHP_RENDER_STATS, and
+ * khp_render's own cases.  KHP_ENOTREADY: moments off, or no tree.
+ * KHP_EUNSUPPORTED: the light-path variant enabled.  A refused call changes no byte
+ * of the state or the framebuffer.  KIRK has no counterpart. */
+typedef struct {
+    float    threshold;    /* a pixel is converged when rel_error <= threshold; >= 0, not NaN (+inf allowed) */
+    uint32_t min_samples;  /* a pixel with count + bad <  min_samples is always active */
+    uint32_t max_samples;  /* a pixel with count + bad >= max_samples is never active; 0: no cap */
+    uint32_t reserved;     /* 0 */
+} khp_adaptive_params;     /* 16 bytes */
+void       khp_adaptive_defaults(khp_adaptive_params* out);   /* 0.05, 8, 0: starting values, not a measured optimum */
+
+typedef struct { uint64_t owned, active, reserved[2]; } khp_adaptive_result;   /* 32 bytes */
+
+khp_status khp_render_adaptive(khp_ctx* ctx, const khp_render_params* p, const khp_adaptive_params* a,
+                               khp_adaptive_result* res /* nullable */, float* out_rgb);
+khp_status khp_adaptive_select_host(const khp_adaptive_params* a, uint32_t first_sample,
+                                    const khp_moments_buffers* state, uint32_t n_owned, const uint32_t* owned,
+                                    uint32_t* active, uint32_t* n_active);   /* no device, no context */
+/* Test hooks.  khp_debug_adaptive_select runs exactly the selection kernels of
+ * khp_render_adaptive over a caller's state (host planes of n_pixels pixels) and
+ * owned list, in scratch of its own: nothing of the context changes.  Only
+ * active[0 .. *n_active) is written.  KHP_EINVAL as for the host entry, and an owned
+ * index >= n_pixels.  khp_debug_adaptive_list returns the last adaptive pass's active
+ * list: *n its length, pixels (or NULL) room for that many (the pass's res->owned
+ * bounds it), select_ms (or NULL) the device time of that pass's selection -- the
+ * three launches and the count's copy, between two HIP events (0 when nothing is
+ * owned).  KHP_ENOTREADY before the first adaptive pass. */
+khp_status khp_debug_adaptive_select(khp_ctx* ctx, const khp_adaptive_params* a, uint32_t first_sample,
+                                     uint32_t n_pixels, const khp_moments_buffers* state, uint32_t n_owned,
+                                     const uint32_t* owned, uint32_t* active, uint32_t* n_active);
+khp_status khp_debug_adaptive_list(khp_ctx* ctx, uint32_t* n, uint32_t* pixels, double* select_ms);
+
 /* ABI 7: the light-path (bidirectional) variant of KIRK's GLSL path tracer,
  * lbb_construction.compute:195-403 builds light subpaths
  * (generatePrimaryLightRays / traceLightRays / shadeLightRays) and
