@@ -5,7 +5,8 @@
 // khp_render_adaptive is a synchronous single pass of the staged batch driver (render.hip:
 // plan_batch, reserve_batch, enqueue_chunk, enqueue_bounce) over the ACTIVE pixels instead of
 // the owned ones: enqueue_frames asks adaptive_list below for the batch's pixel view, and
-// enqueue_accumulate launches k_accumulate_a in place of the running-mean kernels.
+// enqueue_accumulate launches k_accumulate_a in place of the running-mean kernels: the same
+// body (render.hip's accumulate_frame) compiled with the moments fold and without the mean.
 //
 // The active list is the owned list with the inactive pixels removed, order kept, made by
 // three launches on the context stream -- no atomics, no block waiting on another:
@@ -89,24 +90,12 @@ __global__ __launch_bounds__(ADAPT_BLOCK) void k_adapt_scatter(const uint32_t* _
     if (i < n && ((m >> lane) & 1ull)) out[at + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = owned[i];
 }
 
-// The fold of an adaptive batch: k_accumulate_m's shape without the running mean.  A lane per
-// active pixel, its two records loaded once and stored once, the chunk's samples folded in
-// increasing k, and the framebuffer pixel stored from the mean.  One frame (nf == 1): a pixel's
-// samples are adjacent 16-byte paths under either path numbering.
+// The fold of an adaptive batch: k_accumulate_m's body (render.hip: accumulate_frame) without the
+// running mean.  A lane per active pixel, its two records loaded once and stored once, the chunk's
+// samples folded in increasing k, and the framebuffer pixel stored from the mean.  One frame
+// (nf == 1): a pixel's samples are adjacent 16-byte paths under either path numbering.
 __global__ __launch_bounds__(256) void k_accumulate_a(Wave Wv, float* fb, uint32_t fr, MomRec* st) {
-    uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= Wv.P) return;
-    uint32_t pixel = Wv.pix[Wv.p_off + p];
-    MomRec* m = st + 2 * (size_t)pixel;
-    MomRec ma = m[0], mb = m[1];
-    const size_t base = path_index(Wv, fr, p, 0);
-    for (uint32_t s = 0; s < Wv.n_samples; ++s) {
-        const float4 ck = Wv.CK[base + s];
-        mom_fold(ma, mb, ck.x, ck.y, ck.z, Wv.fsample0[fr] + s);
-    }
-    float* o = fb + 3 * (size_t)pixel;
-    o[0] = ma.x; o[1] = ma.y; o[2] = ma.z;
-    m[0] = ma; m[1] = mb;
+    accumulate_frame<false, true>(Wv, fb, fr, st);
 }
 
 // ---- host side ---------------------------------------------------------------------------

@@ -5,91 +5,27 @@
 // The state (khp_ctx::mom) is two MomRec per image pixel, (mean.rgb, n) and (m2.rgb, bad).
 // It is folded by k_accumulate_m / k_accumulate_all_m, which launch_accumulate /
 // launch_accumulate_all (render.hip) pick while khp_ctx::moments_on is set: every
-// schedule ends in those launches, so none has a case of its own here.
+// schedule ends in those launches, so none has a case of its own here.  Both are instances
+// of the accumulate bodies of render.hip (fold_sample, accumulate_frame, accumulate_all),
+// which hold the one definition of the running mean and of the fold beside it.
 //
-//   k_accumulate_m      one frame per launch, a lane per owned pixel;
-//   k_accumulate_all_m  every fused frame in one launch, the samples staged through LDS: a
-//                       thread loads its pixel's two records once and stores them once;
+//   k_accumulate_m      accumulate_frame<true, true>: one frame per launch, a lane per owned pixel;
+//   k_accumulate_all_m  accumulate_all<true>: every fused frame in one launch, the samples staged
+//                       through LDS: a thread loads its pixel's two records once and stores them once;
 //   k_moments_read      a lane per pixel: the two records -> whichever planes were asked
 //                       for, and rel_error from mom_rel_error.
 #pragma once
 
 #include "moments.h"
 
-// k_accumulate's and k_accumulate_all's twins (render.hip), launched in their place while
-// khp_set_moments is on: the same running mean, statement for statement, and beside it the fold of
-// moments.h into the pixel's two 16-byte records (mean.rgb, n) (m2.rgb, bad) of st, which is
-// indexed by image pixel -- two aligned 128-bit loads and two stores per pixel and launch.
+// Launched in place of k_accumulate and k_accumulate_all while khp_set_moments is on: the same
+// bodies (render.hip: accumulate_frame, accumulate_all), compiled with the moments fold beside the
+// running mean.
 __global__ __launch_bounds__(256) void k_accumulate_m(Wave Wv, float* fb, uint32_t fr, MomRec* st) {
-    uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= Wv.P) return;
-    uint32_t pixel = Wv.pix[Wv.p_off + p];
-    float* o = fb + 3 * (size_t)pixel;
-    float r = o[0], g = o[1], b = o[2];
-    MomRec* m = st + 2 * (size_t)pixel;
-    MomRec ma = m[0], mb = m[1];
-    const size_t base = path_index(Wv, fr, p, 0);
-    for (uint32_t s = 0; s < Wv.n_samples; ++s) {
-        const float4 ck = Wv.CK[base + s];
-        float cr = ck.x, cg = ck.y, cb = ck.z;
-        uint32_t k = Wv.fsample0[fr] + s;
-        if (k == 0) {
-            r = cr; g = cg; b = cb;
-        } else {
-            float kk = (float)(k + 1);
-            r = r + (cr - r) / kk;
-            g = g + (cg - g) / kk;
-            b = b + (cb - b) / kk;
-        }
-        mom_fold(ma, mb, cr, cg, cb, k);
-    }
-    o[0] = r; o[1] = g; o[2] = b;
-    m[0] = ma; m[1] = mb;
+    accumulate_frame<true, true>(Wv, fb, fr, st);
 }
-
 __global__ __launch_bounds__(ACC_PIX) void k_accumulate_all_m(Wave Wv, float* fb, MomRec* st) {
-    extern __shared__ float4 stage[];
-    const uint32_t ns = Wv.n_samples, row = ns + 1u;  // +1: rows start on different banks
-    const uint32_t p0 = blockIdx.x * ACC_PIX, np = min(ACC_PIX, Wv.P - p0);
-    const uint32_t p = p0 + threadIdx.x;
-    float r = 0.0f, g = 0.0f, b = 0.0f;
-    float* o = nullptr;
-    MomRec* m = nullptr;
-    MomRec ma = {0.0f, 0.0f, 0.0f, 0u}, mb = {0.0f, 0.0f, 0.0f, 0u};
-    if (threadIdx.x < np) {
-        const uint32_t pixel = Wv.pix[Wv.p_off + p];
-        o = fb + 3 * (size_t)pixel;
-        r = o[0]; g = o[1]; b = o[2];
-        m = st + 2 * (size_t)pixel;
-        ma = m[0]; mb = m[1];
-    }
-    for (uint32_t fr = 0; fr < Wv.n_frames; ++fr) {
-        for (uint32_t j = threadIdx.x; j < np * ns; j += ACC_PIX) {
-            const uint32_t q = j / ns, s = j - q * ns;
-            stage[q * row + s] = Wv.CK[path_index(Wv, fr, p0 + q, s)];
-        }
-        __syncthreads();
-        if (threadIdx.x < np) {
-            for (uint32_t s = 0; s < ns; ++s) {
-                const float4 ck = stage[threadIdx.x * row + s];
-                const uint32_t k = Wv.fsample0[fr] + s;
-                if (k == 0) {
-                    r = ck.x; g = ck.y; b = ck.z;
-                } else {
-                    const float kk = (float)(k + 1);
-                    r = r + (ck.x - r) / kk;
-                    g = g + (ck.y - g) / kk;
-                    b = b + (ck.z - b) / kk;
-                }
-                mom_fold(ma, mb, ck.x, ck.y, ck.z, k);
-            }
-        }
-        __syncthreads();
-    }
-    if (o) {
-        o[0] = r; o[1] = g; o[2] = b;
-        m[0] = ma; m[1] = mb;
-    }
+    accumulate_all<true>(Wv, fb, st);
 }
 
 __global__ __launch_bounds__(256) void k_moments_read(const MomRec* __restrict__ st, uint64_t npix, khp_moments_buffers out) {

@@ -1106,6 +1106,174 @@ __device__ __forceinline__ void block_alloc4(bool p0, bool p1, bool p2, bool p3,
     __syncthreads();  // sh is reused by the next iteration
 }
 
+// KIRK's light occlusion loop (SimpleShader.h:131-141): a light's own surface in front of
+// tmax blocks a shadow or connection ray that no scene object did.
+__device__ __forceinline__ bool occluded_by_light(const DevScene& S, const Ray& r, float tmax) {
+    for (int li = 0; li < S.n_lights; ++li) {
+        float t;
+        if (light_isect(S.lights[li], r, t) && (t < tmax)) return true;
+    }
+    return false;
+}
+
+// The colour a surface hit adds to its path (SimpleShader.h:142-148): the direct light dl
+// that got through, the ambient term AT and, on an emissive hit, ET.  Every site that adds
+// this term -- at once, precomputed into a shadow record, or in a finish -- goes through
+// these operations in this order: that is what keeps the frames bit-equal to the oracle.
+__device__ __forceinline__ v3 deferred_add(v3 dl, v3 Told, v3 AT, bool has_emit, v3 ET) {
+    v3 acc = (mk(0, 0, 0) + dl * Told) + AT;
+    if (has_emit) acc = acc + ET;
+    return acc;
+}
+
+// The per-hit operations of k_shade and k_path (KIRK's traceRay light test,
+// EnvironmentShader / LightShader / SimpleShader / MarschnerHairShader): the path state
+// after bounce `bounce` and, when the NEE colour is nonzero, the shadow ray whose any-hit
+// result decides the deferred colour add (shadow_finish_one, finish_acc).
+struct ShadeOut {
+    v3 T, C;
+    int flags;
+    Ray nr;           // the next extension ray
+    bool emit_ray;    // the path continues with nr
+    bool emit_sh;     // a shadow ray to trace; the colour add is deferred to its finish
+    Ray shr;
+    float sh_tmax;
+    v3 lc, Told, AT, ET;
+    bool has_emit;
+};
+// NEE: next-event estimation towards one light, and the colour add that goes with it.  Without
+// it (the light-path variant) a surface hit whose colour term is due calls connect(s, loc, o, C)
+// in its place: k_shade's connection groups, which add the term to C or leave it to their finish.
+template <bool TEX, uint32_t KINDS, bool NEE = true, class Connect = std::nullptr_t>
+__device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, float lambda, int32_t slot, v3 T, v3 C,
+                                           int flags, uint32_t key, uint32_t bounce, bool last, ShadeOut& o,
+                                           Connect connect = nullptr) {
+    o.nr.o = o.nr.d = mk(0, 0, 0);
+    o.shr.o = o.shr.d = mk(0, 0, 0);
+    o.sh_tmax = 0.0f;
+    o.lc = o.Told = o.AT = o.ET = mk(0, 0, 0);
+    o.has_emit = false;
+    o.emit_sh = false;
+    // KIRK's linear ray-light test (CPU_PathTracer.cpp:185-208)
+    float t_lights = FLT_MAX_;
+    int t_index = -1;
+    for (int li = 0; li < S.n_lights; ++li) {
+        float t = FLT_MAX_;
+        if (light_isect(S.lights[li], r, t)) {
+            t_lights = gmin(t_lights, t);
+            t_index = (t == t_lights) ? li : t_index;
+        }
+    }
+    bool light_hit = false;
+    if (t_lights < lambda) {
+        lambda = t_lights;
+        light_hit = true;
+    }
+    if (lambda == FLT_MAX_) {  // EnvironmentShader::shade
+        C = C + (TEX ? env_color(S, r.d) : mk(S.env.color[0], S.env.color[1], S.env.color[2])) * T;
+        T = mk(0, 0, 0);
+    } else if (light_hit) {    // LightShader::shade
+        C = C + light_emit(S.lights[t_index], r.d) * T;
+        T = mk(0, 0, 0);
+    } else {
+        // normal and hair frame (Cylinder::calcNormal / Triangle::calcNormal), material
+        ShadeCtx s;
+        khp_material mres;
+        const Hit hh{lambda, slot, 0.0f, 0.0f};  // u, v: surface_at recomputes them
+        const v3 nrm = surface_at<TEX>(S, r, hh, s, mres);
+        const v3 loc = follow(r, lambda);
+        const khp_material* m = s.m;
+        float h0 = draw_u01(key, dim_of(bounce, P_HAIR_ALPHA)), h1 = draw_u01(key, dim_of(bounce, P_HAIR_BETA));
+        v3 counter = -normalize(r.d);
+        // NEE setup: SimpleShader::calcDirectLight (SimpleShader.h:101-152) and
+        // MarschnerHairShader::calcDirectLight (MarschnerHairShader.h:87-138)
+        bool need_shadow = false;
+        if (NEE && S.n_lights > 0) {
+            int li = (int)((double)draw_u01(key, dim_of(bounce, P_LIGHT_SEL)) * (double)S.n_lights);
+            const DevLight& L = S.lights[li];
+            float att;
+            Ray h2l = light_dir(L, loc, draw_u01(key, dim_of(bounce, P_LIGHT_0)),
+                                draw_u01(key, dim_of(bounce, P_LIGHT_1)), att);
+            v3 lightpos = h2l.o + h2l.d;
+            h2l.o = h2l.o + faceforward(nrm, h2l.o - lightpos, nrm) * 1e-4f;
+            h2l.d = normalize(h2l.d);
+            if (L.color[0] > 0.0f || L.color[1] > 0.0f || L.color[2] > 0.0f) {
+                v3 fe = bsdf_eval(s, h2l.d, -r.d);
+                float ad = fabsf(dot(h2l.d, nrm));
+                o.lc = mk(L.color[0] * ((att * fe.x) * ad), L.color[1] * ((att * fe.y) * ad),
+                          L.color[2] * ((att * fe.z) * ad));
+                o.sh_tmax = length(lightpos - h2l.o);
+                o.shr = h2l;
+                need_shadow = true;
+            }
+        }
+        v3 ev = bsdf_eval(s, nrm, nrm);
+        v3 amb = mk(S.env.ambient[0], S.env.ambient[1], S.env.ambient[2]) * (ev * ONE_OVER_PI);
+        o.Told = T;
+        o.AT = amb * T;
+        bool add_now = true;  // colour add not left out (a hair's T / TR pass adds none)
+        if (m->shader == KHP_SHADER_MARSCHNER_HAIR) {  // MarschnerHairShader::shade
+            float smp[2] = {0.0f, 0.0f};
+            v3 out;
+            float pdf = 0.0f;
+            bool valid;
+            float hl = 0.0f;   // the lobe draw of hair_lobes.h (lobe instances only)
+            if constexpr (kinds_lobes<KINDS>) hl = draw_u01(key, dim_of(bounce, P_HAIR_LOBE));
+            v3 refl = bsdf_sample<KINDS>(s, counter, nrm, smp, h0, h1, out, pdf, flags, valid, hl, S.hair_lobes);
+            v3 off = out * 1e-4f;
+            if (!(flags & F_SPECULAR)) off = faceforward(-(nrm * 1e-4f), nrm, out);
+            o.nr = make_ray(loc + off, out);
+            if ((flags & F_CYL_T) || (flags & F_CYL_TR)) {
+                need_shadow = false;
+                add_now = false;
+            } else {
+                if (is_zero(refl) || pdf <= 1E-4f || gmax(T.x, gmax(T.y, T.z)) < 0.01f) T = mk(0, 0, 0);
+                else T = T * ((refl * 3.0f) * fabsf(k_cosf(smp[0])));
+            }
+        } else {  // SimpleShader::shade
+            float smp[2] = {draw_u01(key, dim_of(bounce, P_BSDF_0)), draw_u01(key, dim_of(bounce, P_BSDF_1))};
+            v3 out;
+            float pdf = 0.0f;
+            int fl = 0;
+            bool valid;
+            v3 refl = bsdf_sample<KINDS>(s, counter, nrm, smp, h0, h1, out, pdf, fl, valid);
+            if (is_zero(refl) || pdf <= 1E-4f || gmax(T.x, gmax(T.y, T.z)) < 0.01f) {
+                T = mk(0, 0, 0);
+            } else if ((fl & F_EMISSIVE) == F_EMISSIVE) {
+                o.has_emit = true;
+                o.ET = mk(m->emission[0], m->emission[1], m->emission[2]) * T;
+                T = mk(0, 0, 0);
+            } else {
+                float ad = fabsf(dot(out, nrm));
+                T = T * ((refl * ad) / pdf);
+                flags = fl;
+                v3 off = out * 1e-4f;
+                if ((fl & F_SPECULAR) != F_SPECULAR) off = faceforward(-(nrm * 1e-4f), nrm, out);
+                o.nr = make_ray(loc + off, out);
+            }
+        }
+        if constexpr (!NEE) {
+            if (add_now) connect(s, loc, o, C);
+        } else if (add_now) {
+            const v3 lc = o.lc;
+            if (need_shadow && !(lc.x == 0.0f && lc.y == 0.0f && lc.z == 0.0f)) {
+                o.emit_sh = true;  // the colour add waits for the shadow ray
+            } else if (need_shadow) {
+                // Zero light colour (31.7% of the metric row's shadow rays, measured with a
+                // debug counter): the finish's lc * (occ ? 0 : 1) is lc itself for +-0, so the
+                // any-hit result cannot change the colour and the ray is not traced.
+                C = C + deferred_add(mk(0, 0, 0) + lc * 1.0f, o.Told, o.AT, o.has_emit, o.ET);
+            } else {
+                C = C + deferred_add(mk(0, 0, 0), o.Told, o.AT, o.has_emit, o.ET);
+            }
+        }
+    }
+    o.T = T;
+    o.C = C;
+    o.flags = flags;
+    o.emit_ray = !last && !is_zero(T) && !is_zero(o.nr.d);
+}
+
 // TEX: the scene has textured materials or an environment map (a separate
 // instantiation, so untextured scenes keep k_shade's registers).
 #ifndef KHP_SHADE_WAVES
@@ -1124,15 +1292,8 @@ __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_s
         const uint32_t i = !active ? 0u : Wv.perm ? Wv.perm[iv] : q_phys(iv, nf, Wv.cap);
         const bool heavy = active && Wv.heavy[i] != 0;
         bool emit_ray = false, emit_sh = false;
-        Ray nr;
-        nr.o = nr.d = mk(0, 0, 0);
         uint32_t pid = 0;
-        // shadow record payload
-        Ray shr;
-        shr.o = shr.d = mk(0, 0, 0);
-        float sh_tmax = 0.0f;
-        v3 lc = mk(0, 0, 0), Told = mk(0, 0, 0), AT = mk(0, 0, 0), ET = mk(0, 0, 0);
-        bool has_emit = false;
+        ShadeOut so{};   // an active lane's next ray and shadow record payload
         uint32_t bd_head = 0xFFFFFFFFu;  // BD: the group's head record (its rec[4] is written with the destination)
         float4 tfo = make_float4(0.0f, 0.0f, 0.0f, 0.0f), cko = tfo;  // the path state after this bounce
         if (active) {
@@ -1152,186 +1313,67 @@ __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_s
                 tf = Wv.TFq[cur][si];
                 ck = Wv.CKq[cur][si];
             }
-            float lambda = Wv.ht[i];
-            int32_t slot = Wv.hslot[i];
-            v3 T = mk(tf.x, tf.y, tf.z);
-            v3 C = mk(ck.x, ck.y, ck.z);
-            int flags = (int)bits_from_f(tf.w);
-            uint32_t key = bits_from_f(ck.w);
-            // KIRK's linear ray-light test (CPU_PathTracer.cpp:185-208)
-            float t_lights = FLT_MAX_;
-            int t_index = -1;
-            for (int li = 0; li < S.n_lights; ++li) {
-                float t = FLT_MAX_;
-                if (light_isect(S.lights[li], r, t)) {
-                    t_lights = gmin(t_lights, t);
-                    t_index = (t == t_lights) ? li : t_index;
-                }
-            }
-            bool light_hit = false;
-            if (t_lights < lambda) {
-                lambda = t_lights;
-                light_hit = true;
-            }
-            if (lambda == FLT_MAX_) {  // EnvironmentShader::shade
-                C = C + (TEX ? env_color(S, r.d) : mk(S.env.color[0], S.env.color[1], S.env.color[2])) * T;
-                T = mk(0, 0, 0);
-            } else if (light_hit) {    // LightShader::shade
-                C = C + light_emit(S.lights[t_index], r.d) * T;
-                T = mk(0, 0, 0);
-            } else {
-                // normal and hair frame (Cylinder::calcNormal / Triangle::calcNormal), material
-                ShadeCtx s;
-                khp_material mres;
-                const Hit hh{lambda, slot, 0.0f, 0.0f};  // u, v: surface_at recomputes them
-                const v3 nrm = surface_at<TEX>(S, r, hh, s, mres);
-                const v3 loc = follow(r, lambda);
-                const khp_material* m = s.m;
-                float h0 = draw_u01(key, dim_of(bounce, P_HAIR_ALPHA)), h1 = draw_u01(key, dim_of(bounce, P_HAIR_BETA));
-                v3 counter = -normalize(r.d);
-                // NEE setup: SimpleShader::calcDirectLight (SimpleShader.h:101-152) and
-                // MarschnerHairShader::calcDirectLight (MarschnerHairShader.h:87-138)
-                bool need_shadow = false;
-                if (!BD && S.n_lights > 0) {
-                    int li = (int)((double)draw_u01(key, dim_of(bounce, P_LIGHT_SEL)) * (double)S.n_lights);
-                    const DevLight& L = S.lights[li];
-                    float att;
-                    Ray h2l = light_dir(L, loc, draw_u01(key, dim_of(bounce, P_LIGHT_0)),
-                                        draw_u01(key, dim_of(bounce, P_LIGHT_1)), att);
-                    v3 lightpos = h2l.o + h2l.d;
-                    h2l.o = h2l.o + faceforward(nrm, h2l.o - lightpos, nrm) * 1e-4f;
-                    h2l.d = normalize(h2l.d);
-                    if (L.color[0] > 0.0f || L.color[1] > 0.0f || L.color[2] > 0.0f) {
-                        v3 f = bsdf_eval(s, h2l.d, -r.d);
-                        float ad = fabsf(dot(h2l.d, nrm));
-                        lc = mk(L.color[0] * ((att * f.x) * ad), L.color[1] * ((att * f.y) * ad),
-                                L.color[2] * ((att * f.z) * ad));
-                        sh_tmax = length(lightpos - h2l.o);
-                        shr = h2l;
-                        need_shadow = true;
+            const uint32_t key = bits_from_f(ck.w);
+            // BD (shade_core calls it in place of its NEE colour add; unused otherwise):
+            // pt_shade.compute:146-201: connect the hit to every valid vertex of one subpath.
+            // Contributions that are +-0 in every channel cannot change the sum
+            // (it starts at +0), so they get no connection ray.
+            auto connect = [&](const ShadeCtx& s, v3 loc, const ShadeOut& h, v3& C) __attribute__((always_inline)) {
+                uint32_t nv = 0, sp = 0, li = 0;
+                const float4* lv = nullptr;
+                if (S.n_lights > 0) {
+                    const BdptDev& bd = Wv.bd;
+                    sp = (uint32_t)((float)bd.Ns * draw_u01(key, dim_of(bounce, P_LIGHT_0)));
+                    li = (uint32_t)((float)bd.L * draw_u01(key, dim_of(bounce, P_LIGHT_SEL)));
+                    sp = sp < bd.Ns ? sp : bd.Ns - 1u;
+                    li = li < bd.L ? li : bd.L - 1u;
+                    uint32_t fr, p_local, s_local;
+                    path_coords(Wv, pid, fr, p_local, s_local);
+                    const uint32_t q = fr * Wv.n_samples + s_local;
+                    lv = bd.lv + 3 * ((((size_t)q * bd.Ns + sp) * bd.L + li) * bd.J);
+                    for (uint32_t j = 0; j < bd.J; ++j) {
+                        Ray sh;
+                        float tm;
+                        v3 cj;
+                        if (bd_connection(S, bd, lv, j, S.lights[li], s, loc, r.d, bounce, sh, tm, cj) &&
+                            !(cj.x == 0.0f && cj.y == 0.0f && cj.z == 0.0f))
+                            ++nv;
                     }
                 }
-                v3 ev = bsdf_eval(s, nrm, nrm);
-                v3 amb = mk(S.env.ambient[0], S.env.ambient[1], S.env.ambient[2]) * (ev * ONE_OVER_PI);
-                Told = T;
-                AT = amb * T;
-                bool add_now = true;  // colour add not deferred to the shadow kernel
-                if (m->shader == KHP_SHADER_MARSCHNER_HAIR) {  // MarschnerHairShader::shade
-                    float smp[2] = {0.0f, 0.0f};
-                    v3 out;
-                    float pdf = 0.0f;
-                    bool valid;
-                    float hl = 0.0f;   // the lobe draw of hair_lobes.h (lobe instances only)
-                    if constexpr (kinds_lobes<KINDS>) hl = draw_u01(key, dim_of(bounce, P_HAIR_LOBE));
-                    v3 refl = bsdf_sample<KINDS>(s, counter, nrm, smp, h0, h1, out, pdf, flags, valid, hl, S.hair_lobes);
-                    v3 off = out * 1e-4f;
-                    if (!(flags & F_SPECULAR)) off = faceforward(-(nrm * 1e-4f), nrm, out);
-                    nr = make_ray(loc + off, out);
-                    if ((flags & F_CYL_T) || (flags & F_CYL_TR)) {
-                        need_shadow = false;
-                        add_now = false;
-                    } else {
-                        if (is_zero(refl) || pdf <= 1E-4f || gmax(T.x, gmax(T.y, T.z)) < 0.01f) T = mk(0, 0, 0);
-                        else T = T * ((refl * 3.0f) * fabsf(k_cosf(smp[0])));
-                    }
-                } else {  // SimpleShader::shade
-                    float smp[2] = {draw_u01(key, dim_of(bounce, P_BSDF_0)), draw_u01(key, dim_of(bounce, P_BSDF_1))};
-                    v3 out;
-                    float pdf = 0.0f;
-                    int fl = 0;
-                    bool valid;
-                    v3 refl = bsdf_sample<KINDS>(s, counter, nrm, smp, h0, h1, out, pdf, fl, valid);
-                    if (is_zero(refl) || pdf <= 1E-4f || gmax(T.x, gmax(T.y, T.z)) < 0.01f) {
-                        T = mk(0, 0, 0);
-                    } else if ((fl & F_EMISSIVE) == F_EMISSIVE) {
-                        has_emit = true;
-                        ET = mk(m->emission[0], m->emission[1], m->emission[2]) * T;
-                        T = mk(0, 0, 0);
-                    } else {
-                        float ad = fabsf(dot(out, nrm));
-                        T = T * ((refl * ad) / pdf);
-                        flags = fl;
-                        v3 off = out * 1e-4f;
-                        if ((fl & F_SPECULAR) != F_SPECULAR) off = faceforward(-(nrm * 1e-4f), nrm, out);
-                        nr = make_ray(loc + off, out);
-                    }
-                }
-                if (add_now && BD) {
-                    // pt_shade.compute:146-201: connect to every valid vertex of one subpath.
-                    // Contributions that are +-0 in every channel cannot change the sum
-                    // (it starts at +0), so they get no connection ray.
-                    uint32_t nv = 0, sp = 0, li = 0;
-                    const float4* lv = nullptr;
-                    if (S.n_lights > 0) {
-                        const BdptDev& bd = Wv.bd;
-                        sp = (uint32_t)((float)bd.Ns * draw_u01(key, dim_of(bounce, P_LIGHT_0)));
-                        li = (uint32_t)((float)bd.L * draw_u01(key, dim_of(bounce, P_LIGHT_SEL)));
-                        sp = sp < bd.Ns ? sp : bd.Ns - 1u;
-                        li = li < bd.L ? li : bd.L - 1u;
-                        uint32_t fr, p_local, s_local;
-                        path_coords(Wv, pid, fr, p_local, s_local);
-                        const uint32_t q = fr * Wv.n_samples + s_local;
-                        lv = bd.lv + 3 * ((((size_t)q * bd.Ns + sp) * bd.L + li) * bd.J);
-                        for (uint32_t j = 0; j < bd.J; ++j) {
-                            Ray sh;
-                            float tm;
-                            v3 cj;
-                            if (bd_connection(S, bd, lv, j, S.lights[li], s, loc, r.d, bounce, sh, tm, cj) &&
-                                !(cj.x == 0.0f && cj.y == 0.0f && cj.z == 0.0f))
-                                ++nv;
+                if (nv == 0) {
+                    C = C + deferred_add(mk(0, 0, 0), h.Told, h.AT, h.has_emit, h.ET);
+                } else {  // the colour add is left to the group's finish
+                    const BdptDev& bd = Wv.bd;
+                    uint32_t o = wave_alloc_n(nv, &Wv.shq->nsh);
+                    bool head = true;
+                    for (uint32_t j = 0; j < bd.J; ++j) {
+                        Ray sh;
+                        float tm;
+                        v3 cj;
+                        if (!bd_connection(S, bd, lv, j, S.lights[li], s, loc, r.d, bounce, sh, tm, cj) ||
+                            (cj.x == 0.0f && cj.y == 0.0f && cj.z == 0.0f))
+                            continue;
+                        float4* rec = Wv.sh + Wv.shs * (size_t)o++;
+                        rec[0] = make_float4(sh.o.x, sh.o.y, sh.o.z, tm);
+                        rec[1] = make_float4(sh.d.x, sh.d.y, sh.d.z, f_from_bits(pid));
+                        rec[2] = make_float4(cj.x, cj.y, cj.z, h.has_emit ? 1.0f : 0.0f);
+                        rec[3] = make_float4(h.Told.x, h.Told.y, h.Told.z, head ? (float)nv : 0.0f);
+                        if (head) {
+                            bd_head = o - 1u;
+                            if (h.has_emit) rec[5] = make_float4(h.ET.x, h.ET.y, h.ET.z, 0.0f);
                         }
-                    }
-                    if (nv == 0) {
-                        v3 acc = (mk(0, 0, 0) + mk(0, 0, 0) * Told) + AT;
-                        if (has_emit) acc = acc + ET;
-                        C = C + acc;
-                    } else {  // the colour add is left to the group's finish
-                        const BdptDev& bd = Wv.bd;
-                        uint32_t o = wave_alloc_n(nv, &Wv.shq->nsh);
-                        bool head = true;
-                        for (uint32_t j = 0; j < bd.J; ++j) {
-                            Ray sh;
-                            float tm;
-                            v3 cj;
-                            if (!bd_connection(S, bd, lv, j, S.lights[li], s, loc, r.d, bounce, sh, tm, cj) ||
-                                (cj.x == 0.0f && cj.y == 0.0f && cj.z == 0.0f))
-                                continue;
-                            float4* rec = Wv.sh + Wv.shs * (size_t)o++;
-                            rec[0] = make_float4(sh.o.x, sh.o.y, sh.o.z, tm);
-                            rec[1] = make_float4(sh.d.x, sh.d.y, sh.d.z, f_from_bits(pid));
-                            rec[2] = make_float4(cj.x, cj.y, cj.z, has_emit ? 1.0f : 0.0f);
-                            rec[3] = make_float4(Told.x, Told.y, Told.z, head ? (float)nv : 0.0f);
-                            if (head) {
-                                bd_head = o - 1u;
-                                if (has_emit) rec[5] = make_float4(ET.x, ET.y, ET.z, 0.0f);
-                            }
-                            head = false;
-                        }
-                    }
-                } else if (add_now) {
-                    if (need_shadow && !(lc.x == 0.0f && lc.y == 0.0f && lc.z == 0.0f)) {
-                        emit_sh = true;  // colour is added by k_shadow
-                    } else if (need_shadow) {
-                        // Zero light colour (31.7% of the metric row's shadow rays,
-                        // measured with a debug counter): shadow_finish_one's lc * (occ ? 0 : 1)
-                        // is lc itself for +-0, so the any-hit result cannot change the
-                        // colour and the ray is not traced.  Same operations as the finish.
-                        v3 dl = mk(0, 0, 0) + lc * 1.0f;
-                        v3 acc = (mk(0, 0, 0) + dl * Told) + AT;
-                        if (has_emit) acc = acc + ET;
-                        C = C + acc;
-                    } else {
-                        v3 acc = (mk(0, 0, 0) + mk(0, 0, 0) * Told) + AT;
-                        if (has_emit) acc = acc + ET;
-                        C = C + acc;
+                        head = false;
                     }
                 }
-            }
+            };
+            shade_core<TEX, KINDS, !BD>(S, r, Wv.ht[i], Wv.hslot[i], mk(tf.x, tf.y, tf.z), mk(ck.x, ck.y, ck.z),
+                                        (int)bits_from_f(tf.w), key, bounce, last, so, connect);
             // (with a deferred add -- emit_sh or a BD group -- C is unchanged here and the
             // shadow finish adds this bounce's term to wherever the state goes)
-            tfo = make_float4(T.x, T.y, T.z, f_from_bits((uint32_t)flags));
-            cko = make_float4(C.x, C.y, C.z, ck.w);
-            emit_ray = !last && !is_zero(T) && !is_zero(nr.d);
+            tfo = make_float4(so.T.x, so.T.y, so.T.z, f_from_bits((uint32_t)so.flags));
+            cko = make_float4(so.C.x, so.C.y, so.C.z, ck.w);
+            emit_ray = so.emit_ray;
+            emit_sh = so.emit_sh;
         }
         uint32_t qi, si;
         block_alloc4(emit_ray && heavy, emit_ray && !heavy, emit_sh && heavy, emit_sh && !heavy,
@@ -1343,6 +1385,7 @@ __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_s
         // colour CK[pid].  A deferred colour add is told where the state went.
         const uint32_t dest = emit_ray ? qi : (0x80000000u | pid);
         if (emit_ray) {
+            const Ray& nr = so.nr;
             Wv.qo[nxt][0][qi] = nr.o.x; Wv.qo[nxt][1][qi] = nr.o.y; Wv.qo[nxt][2][qi] = nr.o.z;
             Wv.qd[nxt][0][qi] = nr.d.x; Wv.qd[nxt][1][qi] = nr.d.y; Wv.qd[nxt][2][qi] = nr.d.z;
             Wv.qpid[nxt][qi] = pid;
@@ -1357,18 +1400,15 @@ __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_s
             // operations (lc * (occ ? 0 : 1), then (0 + dl * Told) + AT [+ ET]), so the
             // record is 64 B instead of 96 and the finish reads one of them
             float4* rec = Wv.sh + Wv.shs * (size_t)si;
-            rec[0] = make_float4(shr.o.x, shr.o.y, shr.o.z, sh_tmax);
-            rec[1] = make_float4(shr.d.x, shr.d.y, shr.d.z, f_from_bits(dest));
-            const v3 dl_u = mk(0, 0, 0) + lc * 1.0f, dl_o = mk(0, 0, 0) + lc * 0.0f;
-            v3 add_u = (mk(0, 0, 0) + dl_u * Told) + AT, add_o = (mk(0, 0, 0) + dl_o * Told) + AT;
-            if (has_emit) {
-                add_u = add_u + ET;
-                add_o = add_o + ET;
-            }
+            rec[0] = make_float4(so.shr.o.x, so.shr.o.y, so.shr.o.z, so.sh_tmax);
+            rec[1] = make_float4(so.shr.d.x, so.shr.d.y, so.shr.d.z, f_from_bits(dest));
+            const v3 add_u = deferred_add(mk(0, 0, 0) + so.lc * 1.0f, so.Told, so.AT, so.has_emit, so.ET);
+            const v3 add_o = deferred_add(mk(0, 0, 0) + so.lc * 0.0f, so.Told, so.AT, so.has_emit, so.ET);
             rec[2] = make_float4(add_u.x, add_u.y, add_u.z, 0.0f);
             rec[3] = make_float4(add_o.x, add_o.y, add_o.z, 0.0f);
         }
-        if (BD && bd_head != 0xFFFFFFFFu) Wv.sh[Wv.shs * (size_t)bd_head + 4] = make_float4(AT.x, AT.y, AT.z, f_from_bits(dest));
+        if (BD && bd_head != 0xFFFFFFFFu)
+            Wv.sh[Wv.shs * (size_t)bd_head + 4] = make_float4(so.AT.x, so.AT.y, so.AT.z, f_from_bits(dest));
     }
 }
 
@@ -1414,14 +1454,7 @@ __device__ __forceinline__ void shadow_finish_one(const DevScene& S, const Wave&
         Ray r;
         r.o = mk(a.x, a.y, a.z);
         r.d = mk(b.x, b.y, b.z);
-        const float tmax = a.w;
-        for (int li = 0; li < S.n_lights; ++li) {
-            float t;
-            if (light_isect(S.lights[li], r, t) && (t < tmax)) {
-                occ = true;
-                break;
-            }
-        }
+        occ = occluded_by_light(S, r, a.w);
     }
     const float4 acc = rec[occ ? 3 : 2];   // k_shade's precomputed add for this outcome
     float4* dst = state_dest(Wv, nxt, bits_from_f(b.w));
@@ -1447,22 +1480,18 @@ __device__ __forceinline__ void connection_group_finish(const DevScene& S, const
             Ray r;
             r.o = mk(a.x, a.y, a.z);
             r.d = mk(b.x, b.y, b.z);
-            for (int li = 0; li < S.n_lights; ++li) {
-                float t;
-                if (light_isect(S.lights[li], r, t) && (t < a.w)) {
-                    occ = true;
-                    break;
-                }
-            }
+            occ = occluded_by_light(S, r, a.w);
         }
         if (!occ) dl = dl + mk(c.x, c.y, c.z);
     }
     const float4 e = rec[4];
-    v3 acc = (mk(0, 0, 0) + dl * mk(d.x, d.y, d.z)) + mk(e.x, e.y, e.z);
-    if (rec[2].w != 0.0f) {
+    const bool has_emit = rec[2].w != 0.0f;
+    v3 ET = mk(0, 0, 0);
+    if (has_emit) {   // rec[5] is written for an emissive hit only
         const float4 f = rec[5];
-        acc = acc + mk(f.x, f.y, f.z);
+        ET = mk(f.x, f.y, f.z);
     }
+    const v3 acc = deferred_add(dl, mk(d.x, d.y, d.z), mk(e.x, e.y, e.z), has_emit, ET);
     (void)pid;
     float4* dst = state_dest(Wv, nxt, bits_from_f(e.w));
     const float4 ck = *dst;
@@ -1713,164 +1742,11 @@ __global__ void k_ahead_prep(AheadState* a, uint32_t clear, uint32_t own) {
     }
 }
 
-// k_shade's per-hit operations without the light-path variant (KIRK's traceRay
-// light test, EnvironmentShader / LightShader / SimpleShader /
-// MarschnerHairShader): the path state after bounce `bounce` and, when the NEE
-// colour is nonzero, the shadow ray whose any-hit result decides the deferred
-// colour add (shadow_finish_one).
-struct ShadeOut {
-    v3 T, C;
-    int flags;
-    Ray nr;           // the next extension ray
-    bool emit_ray;    // the path continues with nr
-    bool emit_sh;     // a shadow ray to trace; the colour add is deferred to its finish
-    Ray shr;
-    float sh_tmax;
-    v3 lc, Told, AT, ET;
-    bool has_emit;
-};
-template <bool TEX, uint32_t KINDS>
-__device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, float lambda, int32_t slot, v3 T, v3 C,
-                                           int flags, uint32_t key, uint32_t bounce, bool last, ShadeOut& o) {
-    o.nr.o = o.nr.d = mk(0, 0, 0);
-    o.shr.o = o.shr.d = mk(0, 0, 0);
-    o.sh_tmax = 0.0f;
-    o.lc = o.Told = o.AT = o.ET = mk(0, 0, 0);
-    o.has_emit = false;
-    o.emit_sh = false;
-    float t_lights = FLT_MAX_;
-    int t_index = -1;
-    for (int li = 0; li < S.n_lights; ++li) {
-        float t = FLT_MAX_;
-        if (light_isect(S.lights[li], r, t)) {
-            t_lights = gmin(t_lights, t);
-            t_index = (t == t_lights) ? li : t_index;
-        }
-    }
-    bool light_hit = false;
-    if (t_lights < lambda) {
-        lambda = t_lights;
-        light_hit = true;
-    }
-    if (lambda == FLT_MAX_) {
-        C = C + (TEX ? env_color(S, r.d) : mk(S.env.color[0], S.env.color[1], S.env.color[2])) * T;
-        T = mk(0, 0, 0);
-    } else if (light_hit) {
-        C = C + light_emit(S.lights[t_index], r.d) * T;
-        T = mk(0, 0, 0);
-    } else {
-        ShadeCtx s;
-        khp_material mres;
-        const Hit hh{lambda, slot, 0.0f, 0.0f};
-        const v3 nrm = surface_at<TEX>(S, r, hh, s, mres);
-        const v3 loc = follow(r, lambda);
-        const khp_material* m = s.m;
-        float h0 = draw_u01(key, dim_of(bounce, P_HAIR_ALPHA)), h1 = draw_u01(key, dim_of(bounce, P_HAIR_BETA));
-        v3 counter = -normalize(r.d);
-        bool need_shadow = false;
-        if (S.n_lights > 0) {
-            int li = (int)((double)draw_u01(key, dim_of(bounce, P_LIGHT_SEL)) * (double)S.n_lights);
-            const DevLight& L = S.lights[li];
-            float att;
-            Ray h2l = light_dir(L, loc, draw_u01(key, dim_of(bounce, P_LIGHT_0)),
-                                draw_u01(key, dim_of(bounce, P_LIGHT_1)), att);
-            v3 lightpos = h2l.o + h2l.d;
-            h2l.o = h2l.o + faceforward(nrm, h2l.o - lightpos, nrm) * 1e-4f;
-            h2l.d = normalize(h2l.d);
-            if (L.color[0] > 0.0f || L.color[1] > 0.0f || L.color[2] > 0.0f) {
-                v3 f = bsdf_eval(s, h2l.d, -r.d);
-                float ad = fabsf(dot(h2l.d, nrm));
-                o.lc = mk(L.color[0] * ((att * f.x) * ad), L.color[1] * ((att * f.y) * ad),
-                          L.color[2] * ((att * f.z) * ad));
-                o.sh_tmax = length(lightpos - h2l.o);
-                o.shr = h2l;
-                need_shadow = true;
-            }
-        }
-        v3 ev = bsdf_eval(s, nrm, nrm);
-        v3 amb = mk(S.env.ambient[0], S.env.ambient[1], S.env.ambient[2]) * (ev * ONE_OVER_PI);
-        o.Told = T;
-        o.AT = amb * T;
-        bool add_now = true;
-        if (m->shader == KHP_SHADER_MARSCHNER_HAIR) {
-            float smp[2] = {0.0f, 0.0f};
-            v3 out;
-            float pdf = 0.0f;
-            bool valid;
-            float hl = 0.0f;   // the lobe draw of hair_lobes.h (lobe instances only)
-            if constexpr (kinds_lobes<KINDS>) hl = draw_u01(key, dim_of(bounce, P_HAIR_LOBE));
-            v3 refl = bsdf_sample<KINDS>(s, counter, nrm, smp, h0, h1, out, pdf, flags, valid, hl, S.hair_lobes);
-            v3 off = out * 1e-4f;
-            if (!(flags & F_SPECULAR)) off = faceforward(-(nrm * 1e-4f), nrm, out);
-            o.nr = make_ray(loc + off, out);
-            if ((flags & F_CYL_T) || (flags & F_CYL_TR)) {
-                need_shadow = false;
-                add_now = false;
-            } else {
-                if (is_zero(refl) || pdf <= 1E-4f || gmax(T.x, gmax(T.y, T.z)) < 0.01f) T = mk(0, 0, 0);
-                else T = T * ((refl * 3.0f) * fabsf(k_cosf(smp[0])));
-            }
-        } else {
-            float smp[2] = {draw_u01(key, dim_of(bounce, P_BSDF_0)), draw_u01(key, dim_of(bounce, P_BSDF_1))};
-            v3 out;
-            float pdf = 0.0f;
-            int fl = 0;
-            bool valid;
-            v3 refl = bsdf_sample<KINDS>(s, counter, nrm, smp, h0, h1, out, pdf, fl, valid);
-            if (is_zero(refl) || pdf <= 1E-4f || gmax(T.x, gmax(T.y, T.z)) < 0.01f) {
-                T = mk(0, 0, 0);
-            } else if ((fl & F_EMISSIVE) == F_EMISSIVE) {
-                o.has_emit = true;
-                o.ET = mk(m->emission[0], m->emission[1], m->emission[2]) * T;
-                T = mk(0, 0, 0);
-            } else {
-                float ad = fabsf(dot(out, nrm));
-                T = T * ((refl * ad) / pdf);
-                flags = fl;
-                v3 off = out * 1e-4f;
-                if ((fl & F_SPECULAR) != F_SPECULAR) off = faceforward(-(nrm * 1e-4f), nrm, out);
-                o.nr = make_ray(loc + off, out);
-            }
-        }
-        if (add_now) {
-            const v3 lc = o.lc;
-            if (need_shadow && !(lc.x == 0.0f && lc.y == 0.0f && lc.z == 0.0f)) {
-                o.emit_sh = true;  // the colour add waits for the shadow ray
-            } else if (need_shadow) {  // zero light colour: the finish's operations, without the ray (k_shade)
-                v3 dl = mk(0, 0, 0) + lc * 1.0f;
-                v3 acc = (mk(0, 0, 0) + dl * o.Told) + o.AT;
-                if (o.has_emit) acc = acc + o.ET;
-                C = C + acc;
-            } else {
-                v3 acc = (mk(0, 0, 0) + mk(0, 0, 0) * o.Told) + o.AT;
-                if (o.has_emit) acc = acc + o.ET;
-                C = C + acc;
-            }
-        }
-    }
-    o.T = T;
-    o.C = C;
-    o.flags = flags;
-    o.emit_ray = !last && !is_zero(T) && !is_zero(o.nr.d);
-}
-
-// shadow_finish_one's colour term for a traced shadow ray.
+// k_path's finish of a traced shadow ray: the colour term k_shade precomputes for either outcome.
 __device__ __forceinline__ v3 finish_acc(const DevScene& S, const Ray& r, float tmax, bool occ, v3 lc, v3 Told, v3 AT,
                                          bool has_emit, v3 ET) {
-    if (!occ) {
-        for (int li = 0; li < S.n_lights; ++li) {
-            float t;
-            if (light_isect(S.lights[li], r, t) && (t < tmax)) {
-                occ = true;
-                break;
-            }
-        }
-    }
-    v3 l = lc * (occ ? 0.0f : 1.0f);
-    v3 dl = mk(0, 0, 0) + l;
-    v3 acc = (mk(0, 0, 0) + dl * Told) + AT;
-    if (has_emit) acc = acc + ET;
-    return acc;
+    if (!occ) occ = occluded_by_light(S, r, tmax);
+    return deferred_add(mk(0, 0, 0) + lc * (occ ? 0.0f : 1.0f), Told, AT, has_emit, ET);
 }
 
 enum : uint32_t { PS_TRAV = 0u, PS_FIN = 1u, PS_NEW = 2u, PS_BEGIN = 3u, PS_DONE = 4u };
@@ -2278,34 +2154,68 @@ static void launch_path(bool tex, bool wide, bool fur, bool lobes, int grid, hip
 }
 
 // ---- accumulate: PathTracer::drawTexture running mean (CPU_PathTracer.cpp:61-90) -------
-
-// Fused frames are accumulated one frame per launch (fr), in call order.
-__global__ __launch_bounds__(256) void k_accumulate(Wave Wv, float* fb, uint32_t fr) {
-    uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= Wv.P) return;
-    uint32_t pixel = Wv.pix[Wv.p_off + p];
+// The accumulate kernels -- two here, k_accumulate_m and k_accumulate_all_m in moments_dev.h,
+// k_accumulate_a in adaptive_dev.h -- are instances of the two bodies below over one step:
+// MEAN folds the framebuffer's running mean, MOM the pixel's two records of moments.h (st,
+// indexed by image pixel: two aligned 128-bit loads and two stores per pixel and launch).
+// Without MEAN (adaptive passes) the framebuffer pixel is stored from the records' mean.
+struct PixelAcc {
+    float r, g, b;
+    MomRec ma, mb;
+};
+template <bool MEAN, bool MOM>
+__device__ __forceinline__ void acc_load(PixelAcc& a, const float* fb, const MomRec* st, uint32_t pixel) {
+    if (MEAN) {
+        const float* o = fb + 3 * (size_t)pixel;
+        a.r = o[0]; a.g = o[1]; a.b = o[2];
+    }
+    if (MOM) {
+        a.ma = st[2 * (size_t)pixel];
+        a.mb = st[2 * (size_t)pixel + 1];
+    }
+}
+template <bool MEAN, bool MOM>
+__device__ __forceinline__ void acc_store(const PixelAcc& a, float* fb, MomRec* st, uint32_t pixel) {
     float* o = fb + 3 * (size_t)pixel;
-    float r = o[0], g = o[1], b = o[2];
-    const size_t base = path_index(Wv, fr, p, 0);
-    for (uint32_t s = 0; s < Wv.n_samples; ++s) {
-        const float4 ck = Wv.CK[base + s];
-        float cr = ck.x, cg = ck.y, cb = ck.z;
-        uint32_t k = Wv.fsample0[fr] + s;
+    o[0] = MEAN ? a.r : a.ma.x; o[1] = MEAN ? a.g : a.ma.y; o[2] = MEAN ? a.b : a.ma.z;
+    if (MOM) {
+        st[2 * (size_t)pixel] = a.ma;
+        st[2 * (size_t)pixel + 1] = a.mb;
+    }
+}
+// The sample colour ck, whose global sample index is k, into the pixel's accumulators.
+template <bool MEAN, bool MOM>
+__device__ __forceinline__ void fold_sample(PixelAcc& a, float4 ck, uint32_t k) {
+    if (MEAN) {
         if (k == 0) {
-            r = cr; g = cg; b = cb;
+            a.r = ck.x; a.g = ck.y; a.b = ck.z;
         } else {
-            float kk = (float)(k + 1);
-            r = r + (cr - r) / kk;
-            g = g + (cg - g) / kk;
-            b = b + (cb - b) / kk;
+            const float kk = (float)(k + 1);
+            a.r = a.r + (ck.x - a.r) / kk;
+            a.g = a.g + (ck.y - a.g) / kk;
+            a.b = a.b + (ck.z - a.b) / kk;
         }
     }
-    o[0] = r; o[1] = g; o[2] = b;
+    if (MOM) mom_fold(a.ma, a.mb, ck.x, ck.y, ck.z, k);
+}
+
+// One frame (fr) of Wv, a lane per pixel of its view; fused frames take one launch each, in
+// call order.  A pixel's samples of one frame are adjacent 16-byte paths.
+template <bool MEAN, bool MOM>
+__device__ __forceinline__ void accumulate_frame(const Wave& Wv, float* fb, uint32_t fr, MomRec* st) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= Wv.P) return;
+    const uint32_t pixel = Wv.pix[Wv.p_off + p];
+    PixelAcc a;
+    acc_load<MEAN, MOM>(a, fb, st, pixel);
+    const size_t base = path_index(Wv, fr, p, 0);
+    for (uint32_t s = 0; s < Wv.n_samples; ++s) fold_sample<MEAN, MOM>(a, Wv.CK[base + s], Wv.fsample0[fr] + s);
+    acc_store<MEAN, MOM>(a, fb, st, pixel);
 }
 
 // All fused frames of a chunk in one launch (a batch with no gather or snapshot
-// between its frames): the same running mean, frame after frame in call order,
-// with one framebuffer read and write per pixel instead of one per frame.  A
+// between its frames): the same fold, frame after frame in call order, with one
+// read and write of a pixel's accumulators instead of one per frame.  A
 // block of ACC_PIX pixels stages each frame's samples through LDS: the block
 // reads them as whole 16-B-per-lane runs of consecutive samples (a pixel's
 // n_samples colours of one frame are adjacent paths), then every thread folds
@@ -2313,41 +2223,35 @@ __global__ __launch_bounds__(256) void k_accumulate(Wave Wv, float* fb, uint32_t
 // apart with 32 fused frames, fetched 5.6x the bytes (rocprofv3, round 3).
 constexpr uint32_t ACC_PIX = 128;
 constexpr uint32_t ACC_MAX_SAMPLES = 16;  // LDS: ACC_PIX x (n_samples + 1) float4
-__global__ __launch_bounds__(ACC_PIX) void k_accumulate_all(Wave Wv, float* fb) {
+template <bool MOM>
+__device__ __forceinline__ void accumulate_all(const Wave& Wv, float* fb, MomRec* st) {
     extern __shared__ float4 stage[];
     const uint32_t ns = Wv.n_samples, row = ns + 1u;  // +1: rows start on different banks
     const uint32_t p0 = blockIdx.x * ACC_PIX, np = min(ACC_PIX, Wv.P - p0);
-    const uint32_t p = p0 + threadIdx.x;
-    float r = 0.0f, g = 0.0f, b = 0.0f;
-    float* o = nullptr;
-    if (threadIdx.x < np) {
-        o = fb + 3 * (size_t)Wv.pix[Wv.p_off + p];
-        r = o[0]; g = o[1]; b = o[2];
-    }
+    const bool mine = threadIdx.x < np;   // the last block's other threads only help staging
+    const uint32_t pixel = mine ? Wv.pix[Wv.p_off + p0 + threadIdx.x] : 0u;
+    PixelAcc a{};
+    if (mine) acc_load<true, MOM>(a, fb, st, pixel);
     for (uint32_t fr = 0; fr < Wv.n_frames; ++fr) {
         for (uint32_t j = threadIdx.x; j < np * ns; j += ACC_PIX) {
             const uint32_t q = j / ns, s = j - q * ns;
             stage[q * row + s] = Wv.CK[path_index(Wv, fr, p0 + q, s)];
         }
         __syncthreads();
-        if (threadIdx.x < np) {
-            for (uint32_t s = 0; s < ns; ++s) {
-                const float4 ck = stage[threadIdx.x * row + s];
-                const uint32_t k = Wv.fsample0[fr] + s;
-                if (k == 0) {
-                    r = ck.x; g = ck.y; b = ck.z;
-                } else {
-                    const float kk = (float)(k + 1);
-                    r = r + (ck.x - r) / kk;
-                    g = g + (ck.y - g) / kk;
-                    b = b + (ck.z - b) / kk;
-                }
-            }
-        }
+        if (mine)
+            for (uint32_t s = 0; s < ns; ++s) fold_sample<true, MOM>(a, stage[threadIdx.x * row + s], Wv.fsample0[fr] + s);
         __syncthreads();
     }
-    if (o) { o[0] = r; o[1] = g; o[2] = b; }
+    if (mine) acc_store<true, MOM>(a, fb, st, pixel);
 }
+
+__global__ __launch_bounds__(256) void k_accumulate(Wave Wv, float* fb, uint32_t fr) {
+    accumulate_frame<true, false>(Wv, fb, fr, nullptr);
+}
+__global__ __launch_bounds__(ACC_PIX) void k_accumulate_all(Wave Wv, float* fb) {
+    accumulate_all<false>(Wv, fb, nullptr);
+}
+
 
 // ---- output stage: Texture::setPixel byte conversion and Tonemapper::map ---------------
 // Texture::toByte (Texture.h:252-254): (uchar)std::max(std::min(f * 255, 255), 0).

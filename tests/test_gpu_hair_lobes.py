@@ -359,6 +359,21 @@ def test_render_ahead_0_equals_3(scene, lobes_frame):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("name", ["zoo", "textured"])
+def test_lobe_instances_of_scenes_that_are_not_fur_only(name):
+    """The scenes above are fur-only, so they reach one of the three lobe instances of k_shade.  The other two --
+    every BSDF kind, untextured (zoo) and textured -- are reached here, against the oracle: it traces R alone,
+    so the fibres carry the d'Eon BSDF, which the lobe set does not touch, and the frame must be the oracle's."""
+    sd = S.build_config(name, width=32, height=32, n_strands=100)
+    for m in sd.materials:
+        if m.bsdf == N.BSDF_NAMES.index("MarschnerHairBSDF"):
+            m.bsdf = N.BSDF_NAMES.index("DEonHairBSDF")
+    want = oracle_ffi.Oracle(sd).render(32, 32, 2, 3, threads=8)
+    with _Ctx(sd, ALL_LOBES, **WAVEFRONT) as c:
+        assert same(c.render(32, 32, 2, 3), want)
+
+
+@pytest.mark.gpu
 def test_three_ranks_gathered_equal_one_context(scene, lobes_frame):
     from ba_pathtracing_fur_amd.pathtracer import HipContext, comm_init_local
     ctxs = [HipContext(0) for _ in range(3)]
