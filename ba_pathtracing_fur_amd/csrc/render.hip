@@ -2742,6 +2742,7 @@ struct khp_ctx {
     NextCall series;   // the last synchronous single-pass call, first_sample advanced by its spp
     std::shared_ptr<struct AovState> aov;   // khp_render_aov's own scratch (aov.h), made by its first call
     std::shared_ptr<struct DnState> dn;     // khp_denoise's own scratch (denoise_dev.h), made by its first call
+    std::shared_ptr<struct DnvState> dnv;   // khp_denoise_var's own scratch (denoise_var_dev.h), made by its first call
     // khp_set_moments (moments_dev.h): the per-pixel sample moments beside the framebuffer, two MomRec per
     // image pixel, made and zeroed with it (moments_remake); mom_stage: khp_read_moments' host callers
     bool moments_on = false;
@@ -5012,6 +5013,7 @@ extern "C" khp_status khp_debug_queue(khp_ctx* c, uint32_t* n, float* orig, floa
 #include "debug_query.h"   // ABI 15: khp_debug_surface / _bsdf_sample / _bsdf_eval / _light_dir / _light_isect
 #include "aov.h"           // khp_render_aov: per-pixel first-hit feature buffers
 #include "denoise_dev.h"   // khp_denoise: the guided a-trous filter over those buffers
+#include "denoise_var_dev.h"   // khp_denoise_var: the same filter guided by measured variance
 
 extern "C" khp_status khp_read_framebuffer(khp_ctx* c, float* out_rgb) {
     if (c) {  // complete asynchronous frames first

@@ -183,6 +183,28 @@ class DenoiseParams(ctypes.Structure):
         return p
 
 
+NOISE_PLANE, NOISE_MOMENTS, NOISE_CONTEXT = 0, 1, 2
+
+
+class DenoiseNoise(ctypes.Structure):
+    """khp_denoise_noise (48 bytes): where khp_denoise_var takes each pixel's measured variance from,
+    the prefilter, the floor and the optional filtered-variance output."""
+    _fields_ = [("source", c_uint32), ("prefilter", c_uint32), ("floor", c_float), ("reserved", c_uint32),
+                ("variance", POINTER(c_float)), ("m2", POINTER(c_float)), ("count", POINTER(c_uint32)),
+                ("out_variance", POINTER(c_float))]
+
+    @classmethod
+    def defaults(cls, **kw) -> "DenoiseNoise":
+        """khp_denoise_noise_defaults (KHP_NOISE_PLANE, the trimmed prefilter, floor 1e-6, no planes) with fields changed."""
+        p = cls()
+        load_library().khp_denoise_noise_defaults(ctypes.byref(p))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_) or k == "reserved":
+                raise AttributeError(f"khp_denoise_noise has no field {k}")
+            setattr(p, k, v)
+        return p
+
+
 MOMENTS_DEVICE = 1 << 0
 
 
@@ -282,7 +304,8 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_debug_light_paths", "khp_debug_bdpt_connect", "khp_debug_img_connect", "khp_denoise_params_defaults",
             "khp_denoise", "khp_denoise_host", "khp_moments_defaults", "khp_set_moments", "khp_get_moments",
             "khp_read_moments", "khp_moments_fold_host", "khp_adaptive_defaults", "khp_render_adaptive",
-            "khp_adaptive_select_host", "khp_debug_adaptive_select", "khp_debug_adaptive_list"]
+            "khp_adaptive_select_host", "khp_debug_adaptive_select", "khp_debug_adaptive_list",
+            "khp_denoise_noise_defaults", "khp_denoise_var", "khp_denoise_var_host"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
 ABI_VERSION = 17
@@ -324,6 +347,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_denoise_params_defaults": (None, [P(DenoiseParams)]),
         "khp_denoise": (c_int, [c_void_p, P(DenoiseParams), c_void_p, P(AovBuffers), c_void_p]),
         "khp_denoise_host": (c_int, [P(DenoiseParams), c_void_p, P(AovBuffers), c_void_p]),
+        "khp_denoise_noise_defaults": (None, [P(DenoiseNoise)]),
+        "khp_denoise_var": (c_int, [c_void_p, P(DenoiseParams), c_void_p, P(AovBuffers), P(DenoiseNoise), c_void_p]),
+        "khp_denoise_var_host": (c_int, [P(DenoiseParams), c_void_p, P(AovBuffers), P(DenoiseNoise), c_void_p]),
         "khp_moments_defaults": (None, [P(Moments)]),
         "khp_set_moments": (c_int, [c_void_p, P(Moments)]),
         "khp_get_moments": (c_int, [c_void_p, P(Moments)]),

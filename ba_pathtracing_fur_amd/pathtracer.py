@@ -307,6 +307,43 @@ class HipContext:
         del keep
         return out
 
+    def denoise_var(self, width, height, guides: dict, colour=None, variance=None, moments=None, out=None,
+                    out_variance=False, device: bool = False, **params):
+        """khp_denoise_var: denoise()'s filter with sigma_color in standard deviations
+        of each pixel's measured noise.  The noise is `variance`, an (H, W) float32 plane holding the
+        variance of each pixel's mean (channels summed), or `moments`, the dict read_moments returns
+        (its m2 and count are used); with neither it is this context's moments state, read in place
+        (set_moments(True) first), and `colour=None` is then the moments' mean -- otherwise the
+        framebuffer, as for denoise().  `out_variance`: True, or an (H, W) array to write into, to
+        get the filtered variance too (+inf where unknown).  device=True: every array is a
+        DeviceBuffer of this context (out is then required).  **params: khp_denoise_params fields
+        as for denoise() (demodulate is refused: KHP_EUNSUPPORTED), and prefilter (0 / 1) and floor
+        of khp_denoise_noise.  Returns out, or (out, out_variance) when that was asked for."""
+        params = dict(params)
+        z, ov, keep_z = _noise_args(self, width, height, variance, moments, out_variance, device, params, True)
+        p, buf, keep = _denoise_args(width, height, guides, device, params)
+        if device:
+            for name, b in (("colour", colour), ("out", out)):
+                if b is not None and not isinstance(b, DeviceBuffer):
+                    raise ValueError(f"{name}: a DeviceBuffer is needed with device=True")
+                if b is not None and b.nbytes < 12 * width * height:
+                    raise ValueError(f"{name}: a DeviceBuffer of {12 * width * height} bytes is needed")
+            if out is None:
+                raise ValueError("out: a DeviceBuffer is needed with device=True")
+            cptr, optr = (colour.ptr if colour is not None else None), out.ptr
+        else:
+            if colour is not None:
+                _frame_check("colour", colour, width, height)
+            if out is None:
+                out = np.zeros((height, width, 3), np.float32)
+            _frame_check("out", out, width, height)
+            cptr = colour.ctypes.data_as(ctypes.c_void_p) if colour is not None else None
+            optr = out.ctypes.data_as(ctypes.c_void_p)
+        N.check(self.lib, self.lib.khp_denoise_var(self.ptr, ctypes.byref(p), cptr, ctypes.byref(buf), ctypes.byref(z), optr),
+                "khp_denoise_var")
+        del keep, keep_z
+        return out if ov is None else (out, ov)
+
     MOMENTS_PLANES = tuple(N.MOMENTS_PLANES)   # mean, m2, count, bad, rel_error
 
     def set_moments(self, enabled: bool) -> bool:
@@ -752,6 +789,69 @@ def denoise_host(width, height, guides: dict, colour: np.ndarray, out: np.ndarra
                                       out.ctypes.data_as(ctypes.c_void_p)), "khp_denoise_host")
     del keep
     return out
+
+
+def _noise_args(ctx, width, height, variance, moments, out_variance, device, params, has_context):
+    """khp_denoise_noise of a denoise_var call, its planes checked first (dtype, shape, or DeviceBuffer
+    size) as _denoise_args checks the guides; `prefilter` and `floor` are taken out of `params`.
+    Returns (the struct, the out_variance array or None, keep-alives)."""
+    kw = {k: params.pop(k) for k in ("prefilter", "floor") if k in params}
+    if variance is not None and moments is not None:
+        raise ValueError("variance= and moments= are two sources of the noise: give one")
+    z, keep = N.DenoiseNoise.defaults(**kw), []
+
+    def plane(name, a, tail, dtype):
+        shape = (height, width) + tail
+        if device:
+            need = int(np.prod(shape)) * 4
+            if not isinstance(a, DeviceBuffer) or a.nbytes < need:
+                raise ValueError(f"{name}: a DeviceBuffer of {need} bytes is needed with device=True")
+            ptr = a.ptr
+        else:
+            if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError(f"{name}: a C-contiguous {np.dtype(dtype).name} array of shape {shape} is needed")
+            ptr = a.ctypes.data
+        keep.append(a)
+        return ctypes.cast(ptr, ctypes.POINTER(ctypes.c_float if dtype == np.float32 else ctypes.c_uint32))
+
+    if variance is not None:
+        z.source = N.NOISE_PLANE
+        z.variance = plane("variance", variance, (), np.float32)
+    elif moments is not None:
+        z.source = N.NOISE_MOMENTS
+        z.m2 = plane("moments['m2']", moments["m2"], (3,), np.float32)
+        z.count = plane("moments['count']", moments["count"], (), np.uint32)
+    elif has_context:
+        z.source = N.NOISE_CONTEXT
+    else:
+        raise ValueError("variance= or moments= is needed: there is no context whose moments to read")
+    ov = None
+    if out_variance is not None and out_variance is not False:
+        if out_variance is True:
+            ov = DeviceBuffer(ctx, 4 * width * height) if device else np.zeros((height, width), np.float32)
+        else:
+            ov = out_variance
+        z.out_variance = plane("out_variance", ov, (), np.float32)
+    return z, ov, keep
+
+
+def denoise_var_host(width, height, guides: dict, colour: np.ndarray, variance=None, moments=None,
+                     out: np.ndarray | None = None, out_variance=False, **params):
+    """khp_denoise_var_host: HipContext.denoise_var's filter as a plain host loop over the same
+    per-pixel functions -- no device, no context, the same bits.  numpy arrays only, and the noise is
+    `variance` or `moments`.  Returns out, or (out, out_variance) when that was asked for."""
+    params = dict(params)
+    z, ov, keep_z = _noise_args(None, width, height, variance, moments, out_variance, False, params, False)
+    p, buf, keep = _denoise_args(width, height, guides, False, params)
+    _frame_check("colour", colour, width, height)
+    if out is None:
+        out = np.zeros((height, width, 3), np.float32)
+    _frame_check("out", out, width, height)
+    lib = N.load_library()
+    N.check(lib, lib.khp_denoise_var_host(ctypes.byref(p), colour.ctypes.data_as(ctypes.c_void_p), ctypes.byref(buf),
+                                          ctypes.byref(z), out.ctypes.data_as(ctypes.c_void_p)), "khp_denoise_var_host")
+    del keep, keep_z
+    return out if ov is None else (out, ov)
 
 
 def moments_fold_host(samples: np.ndarray, first_sample: int = 0, state: dict | None = None) -> dict:

@@ -482,6 +482,72 @@ khp_status khp_denoise(khp_ctx* ctx, const khp_denoise_params* p, const float* c
 khp_status khp_denoise_host(const khp_denoise_params* p, const float* colour,
                             const khp_aov_buffers* guides, float* out);   /* no device, no context */
 
+/* ---- the same filter guided by measured variance --------------------------------
+ * khp_denoise_var is khp_denoise's a-trous scheme with the colour distance divided,
+ * per pixel, by the measured variance of that pixel's mean: sigma_color is then in
+ * standard deviations of the pixel's own noise, not in radiance units, so the same
+ * call is right at 4 samples per pixel and at 400.  The variance is filtered along
+ * with the colour and can be returned.  p is khp_denoise's struct with the same
+ * meanings but for sigma_color (0 still turns the term off); the same bits from
+ * khp_denoise_var (gfx950 kernels) and khp_denoise_var_host.  The definition,
+ * operation by operation, is DESIGN.md §17; what is not restated there is §13's.
+ *   prepare  per pixel a variance v and a flag known.  PLANE: u = variance[p].
+ *            MOMENTS and CONTEXT: n = count, nf = (float)n, s = (m2.r + m2.g) + m2.b,
+ *            u = s / (nf * (nf - 1.0f)) when n >= 2 (rel_error's radicand).  known =
+ *            (PLANE or n >= 2) and u finite and u >= 0; v = known ? u : +0.
+ *   iterate  before the taps, per pixel: prefilter 0: kbar = known, vbar = v;
+ *            prefilter 1: over the 3 x 3 taps at spacing 1 inside the image and known,
+ *            weights g[dy] g[dx], g = {1/4, 1/2, 1/4}, dy outer and dx inner, vbar =
+ *            sum(g v) / sum(g) WITHOUT the first tap holding the largest v (kept when
+ *            it is the only known tap), kbar = sum(g) > 0.  The largest tap is left out,
+ *            never subtracted.  The colour term is on iff sigma_color > 0, the pixel is
+ *            finite and kbar; then a tap adds d2(c_p, c_q) * icv to X, icv = (1 /
+ *            sigma_color^2) / (vbar + floor).  Along the taps that count and are known,
+ *            va += (w * w) * v_q and wk += w; if any tap counted, known' = wk > 0 and
+ *            v' = known' ? va / (wk * wk) : +0, else v and known stay.
+ *   finish   out as khp_denoise without DEMODULATE; out_variance = known ? v : +inf.
+ * With sigma_color == 0 out is khp_denoise's bit for bit.  A pixel whose variance is
+ * unknown filters with its colour term off, like a pixel that is not finite.  One
+ * firefly's huge variance does not loosen its neighbours' colour term (the trimmed
+ * prefilter), so it does not spread; it is not repaired either: the clamp is khp_denoise's.
+ *
+ * KHP_DENOISE_DEVICE covers every pointer, variance, m2, count and out_variance
+ * included.  KHP_DENOISE_DEMODULATE is KHP_EUNSUPPORTED here: a scalar variance has
+ * no per-channel albedo division (and demodulation is off by default, Marschner's R
+ * radiance not carrying the diffuse colour).  out == colour is allowed.
+ *
+ * KHP_NOISE_CONTEXT reads the context's moments state in place (khp_set_moments on,
+ * width and height the framebuffer's); with it colour == NULL is the moments' mean,
+ * finite everywhere, read in place too; a caller's colour is allowed.  With the other
+ * sources colour == NULL is the framebuffer as for khp_denoise.  Either way the call
+ * completes asynchronous frames first and writes nothing of the context; with a
+ * caller's colour and another source it touches no context state.
+ *
+ * KHP_EINVAL (checked before the context is touched, khp_last_error names the cause):
+ * khp_denoise's cases; a null noise; an unknown source or prefilter; reserved != 0;
+ * a floor negative or not finite; the source's plane(s) NULL (planes of the other
+ * sources are ignored and never read); KHP_NOISE_CONTEXT at the host entry or with
+ * another size than the framebuffer's.  KHP_ENOTREADY: KHP_NOISE_CONTEXT with moments
+ * off or nothing rendered.  KIRK has no counterpart. */
+#define KHP_NOISE_PLANE   0u  /* variance: [H][W], the variance of the pixel's MEAN, channels summed */
+#define KHP_NOISE_MOMENTS 1u  /* m2 [H][W][3] and count [H][W], as khp_read_moments writes them */
+#define KHP_NOISE_CONTEXT 2u  /* khp_denoise_var only: the context's moments state, read in place */
+typedef struct {
+    uint32_t source;          /* KHP_NOISE_* */
+    uint32_t prefilter;       /* 0: the pixel's own variance; 1 (default): trimmed 3 x 3 (above) */
+    float    floor;           /* finite, >= 0; added to the variance before the divide (default 1e-6f) */
+    uint32_t reserved;        /* 0 */
+    const float*    variance; /* PLANE */
+    const float*    m2;       /* MOMENTS */
+    const uint32_t* count;    /* MOMENTS */
+    float*          out_variance;  /* [H][W] or NULL: the filtered variance, +inf where unknown */
+} khp_denoise_noise;          /* 48 bytes */
+void       khp_denoise_noise_defaults(khp_denoise_noise* out);   /* PLANE, 1, 1e-6f, 0, NULLs */
+khp_status khp_denoise_var(khp_ctx* ctx, const khp_denoise_params* p, const float* colour,
+                           const khp_aov_buffers* guides, const khp_denoise_noise* noise, float* out);
+khp_status khp_denoise_var_host(const khp_denoise_params* p, const float* colour,
+                                const khp_aov_buffers* guides, const khp_denoise_noise* noise, float* out);
+
 /* ---- per-pixel sample moments: robust mean, variance, error plane --------------
  * An opt-in second accumulator beside the framebuffer.  Per pixel it holds n, the
  * count of finite samples, their mean, M2, their sum of squared deviations

@@ -211,6 +211,19 @@ class Context {
     void denoise(const khp_denoise_params& p, const float* colour, const khp_aov_buffers& guides, float* out) {
         check(khp_denoise(c_, &p, colour, &guides, out), "khp_denoise");
     }
+    // The same filter with sigma_color in standard deviations of each pixel's measured noise
+    // (khp_denoise_var).  noise from noise_defaults(): source KHP_NOISE_CONTEXT reads the moments
+    // state in place (set_moments first), and colour == nullptr is then the moments' mean.
+    static khp_denoise_noise noise_defaults(uint32_t source = KHP_NOISE_CONTEXT) {
+        khp_denoise_noise n;
+        khp_denoise_noise_defaults(&n);
+        n.source = source;
+        return n;
+    }
+    void denoise_var(const khp_denoise_params& p, const float* colour, const khp_aov_buffers& guides,
+                     const khp_denoise_noise& noise, float* out) {
+        check(khp_denoise_var(c_, &p, colour, &guides, &noise, out), "khp_denoise_var");
+    }
     // KHP_RENDER_ASYNC renders are complete (and accumulated in call order) after sync()
     void sync() { check(khp_sync(c_), "khp_sync"); }
     void read_framebuffer(float* out_rgb) { check(khp_read_framebuffer(c_, out_rgb), "khp_read_framebuffer"); }
