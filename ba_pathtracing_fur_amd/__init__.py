@@ -22,13 +22,16 @@ def set_hw_queues(n: int = 8) -> None:
 from . import native  # noqa: E402,F401
 from .native import (AOV_CHANNELS, DENOISE_DEMODULATE, DENOISE_DEVICE, HAIR_LOBE_R, HAIR_LOBE_TRT,  # noqa: E402
                      HAIR_LOBE_TT, MOMENTS_DEVICE, MOMENTS_PLANES, NOISE_CONTEXT, NOISE_MOMENTS, NOISE_PLANE,
-                     AdaptiveParams, AovBuffers, DenoiseNoise, DenoiseParams)
-from .pathtracer import (BVH, BsdfFactory, HipContext, PathTracer, ShaderFactory, adaptive_select_host,  # noqa: E402
-                         comm_unique_id, denoise_host, denoise_var_host, moments_fold_host, moments_variance)
+                     REPROJECT_DEVICE, REPROJECT_MATCH_OBJECT, AdaptiveParams, AovBuffers, DenoiseNoise, DenoiseParams,
+                     ReprojectFrame, ReprojectOut, ReprojectParams)
+from .pathtracer import (BVH, BsdfFactory, HipContext, PathTracer, ShaderFactory, TemporalAccumulator,  # noqa: E402
+                         adaptive_select_host, comm_unique_id, denoise_host, denoise_var_host, moments_fold_host,
+                         moments_variance, reproject_host)
 from .scenes import SceneData, build_config  # noqa: E402
 
 __all__ = ["set_hw_queues", "native", "BVH", "BsdfFactory", "HipContext", "PathTracer", "ShaderFactory", "SceneData",
            "build_config", "comm_unique_id", "HAIR_LOBE_R", "HAIR_LOBE_TT", "HAIR_LOBE_TRT", "AovBuffers",
            "AOV_CHANNELS", "DenoiseParams", "DENOISE_DEVICE", "DENOISE_DEMODULATE", "denoise_host", "MOMENTS_DEVICE",
            "MOMENTS_PLANES", "moments_fold_host", "moments_variance", "AdaptiveParams", "adaptive_select_host", "DenoiseNoise",
-           "NOISE_PLANE", "NOISE_MOMENTS", "NOISE_CONTEXT", "denoise_var_host"]
+           "NOISE_PLANE", "NOISE_MOMENTS", "NOISE_CONTEXT", "denoise_var_host", "ReprojectParams", "ReprojectFrame",
+           "ReprojectOut", "REPROJECT_DEVICE", "REPROJECT_MATCH_OBJECT", "reproject_host", "TemporalAccumulator"]

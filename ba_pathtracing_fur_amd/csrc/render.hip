@@ -2748,6 +2748,7 @@ struct khp_ctx {
     bool moments_on = false;
     DevMem mom, mom_stage;
     std::shared_ptr<struct AdaptState> ad;  // khp_render_adaptive's own scratch (adaptive_dev.h), made by its first call
+    std::shared_ptr<struct RpState> rp;     // khp_reproject's own staging area (reproject_dev.h), made by its first call
 };
 constexpr size_t LG_SLOTS = 64;
 
@@ -5686,3 +5687,4 @@ extern "C" khp_status khp_debug_leaf_reuse(khp_ctx* c, unsigned long long* out) 
 // khp_read_moments.  Last, so that every kernel above keeps its place in the code object.
 #include "moments_dev.h"
 #include "adaptive_dev.h"   // khp_render_adaptive: passes over the unconverged pixels only
+#include "reproject_dev.h"  // khp_reproject: carry the previous camera's frame into the current one

@@ -205,6 +205,44 @@ class DenoiseNoise(ctypes.Structure):
         return p
 
 
+REPROJECT_DEVICE = 1 << 0
+REPROJECT_MATCH_OBJECT = 1 << 1
+
+
+class ReprojectParams(ctypes.Structure):
+    """khp_reproject_params (48 bytes): the frame size, flags, the current frame's weight, the history cap and
+    the four tolerances of the tap tests."""
+    _fields_ = [("width", c_uint32), ("height", c_uint32), ("flags", c_uint32), ("samples", c_float),
+                ("max_history", c_float), ("depth_tol", c_float), ("normal_tol", c_float), ("tangent_tol", c_float),
+                ("coverage_tol", c_float), ("reserved", c_uint32 * 3)]
+
+    @classmethod
+    def defaults(cls, **kw) -> "ReprojectParams":
+        """khp_reproject_params_defaults (samples 1, max_history 32, tolerances 0.05 / off / 0.25 / 0.5: starting
+        values, not a measured optimum) with fields changed."""
+        p = cls()
+        load_library().khp_reproject_params_defaults(ctypes.byref(p))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_) or k == "reserved":
+                raise AttributeError(f"khp_reproject_params has no field {k}")
+            setattr(p, k, v)
+        return p
+
+
+class ReprojectFrame(ctypes.Structure):
+    """khp_reproject_frame (128 bytes): a frame's camera, colour, variance or NULL, length (the history only)
+    and the planes khp_render_aov wrote with that camera."""
+    _fields_ = [("camera", Camera), ("reserved", c_uint32), ("colour", POINTER(c_float)), ("variance", POINTER(c_float)),
+                ("length", POINTER(c_float)), ("aov", AovBuffers)]
+
+
+class ReprojectOut(ctypes.Structure):
+    """khp_reproject_out (32 bytes): the blended colour, the new length, the propagated variance (+inf where
+    unknown) and the motion vectors (H, W, 2); a null plane is not written."""
+    _fields_ = [("colour", POINTER(c_float)), ("length", POINTER(c_float)), ("variance", POINTER(c_float)),
+                ("motion", POINTER(c_float))]
+
+
 MOMENTS_DEVICE = 1 << 0
 
 
@@ -305,7 +343,8 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_denoise", "khp_denoise_host", "khp_moments_defaults", "khp_set_moments", "khp_get_moments",
             "khp_read_moments", "khp_moments_fold_host", "khp_adaptive_defaults", "khp_render_adaptive",
             "khp_adaptive_select_host", "khp_debug_adaptive_select", "khp_debug_adaptive_list",
-            "khp_denoise_noise_defaults", "khp_denoise_var", "khp_denoise_var_host"]
+            "khp_denoise_noise_defaults", "khp_denoise_var", "khp_denoise_var_host",
+            "khp_reproject_params_defaults", "khp_reproject", "khp_reproject_host"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
 ABI_VERSION = 17
@@ -350,6 +389,9 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_denoise_noise_defaults": (None, [P(DenoiseNoise)]),
         "khp_denoise_var": (c_int, [c_void_p, P(DenoiseParams), c_void_p, P(AovBuffers), P(DenoiseNoise), c_void_p]),
         "khp_denoise_var_host": (c_int, [P(DenoiseParams), c_void_p, P(AovBuffers), P(DenoiseNoise), c_void_p]),
+        "khp_reproject_params_defaults": (None, [P(ReprojectParams)]),
+        "khp_reproject": (c_int, [c_void_p, P(ReprojectParams), P(ReprojectFrame), P(ReprojectFrame), P(ReprojectOut)]),
+        "khp_reproject_host": (c_int, [P(ReprojectParams), P(ReprojectFrame), P(ReprojectFrame), P(ReprojectOut)]),
         "khp_moments_defaults": (None, [P(Moments)]),
         "khp_set_moments": (c_int, [c_void_p, P(Moments)]),
         "khp_get_moments": (c_int, [c_void_p, P(Moments)]),

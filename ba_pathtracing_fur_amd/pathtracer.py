@@ -344,6 +344,27 @@ class HipContext:
         del keep, keep_z
         return out if ov is None else (out, ov)
 
+    def reproject(self, width, height, cur: dict, hist: dict | None = None, out: dict | None = None,
+                  device: bool = False, **params) -> dict:
+        """khp_reproject: carry the previous camera's frame `hist` into the current frame
+        `cur` and blend.  A frame is a dict: "camera" (an N.Camera), "colour" (H, W, 3), "aov" (the dict
+        render_aov returned with that camera; `cur` needs depth and coverage, the rest as the enabled
+        tests ask), optionally "variance" (H, W: the variance of each pixel's mean, channels summed), and
+        for `hist` "length" (H, W: the effective samples behind each pixel).  hist=None starts a history.
+        Returns a dict of the outputs "colour", "length", "variance" (+inf where unknown) and "motion"
+        (H, W, 2): new arrays, or those of `out` (a value of None leaves that output out; out["colour"]
+        may be cur["colour"]).  The returned dict plus cur's camera and aov is the next call's `hist`.
+        device=True: every array is a DeviceBuffer of this context.  **params: khp_reproject_params
+        fields over khp_reproject_params_defaults (samples, max_history, depth_tol, normal_tol,
+        tangent_tol, coverage_tol, flags; match_object=True sets KHP_REPROJECT_MATCH_OBJECT).  Touches no
+        state of the context."""
+        p, cf, hf, o, res, keep = _reproject_args(self, width, height, cur, hist, out, device, params)
+        N.check(self.lib, self.lib.khp_reproject(self.ptr, ctypes.byref(p), ctypes.byref(cf),
+                                                 ctypes.byref(hf) if hf is not None else None, ctypes.byref(o)),
+                "khp_reproject")
+        del keep
+        return res
+
     MOMENTS_PLANES = tuple(N.MOMENTS_PLANES)   # mean, m2, count, bad, rel_error
 
     def set_moments(self, enabled: bool) -> bool:
@@ -852,6 +873,149 @@ def denoise_var_host(width, height, guides: dict, colour: np.ndarray, variance=N
                                           ctypes.byref(z), out.ctypes.data_as(ctypes.c_void_p)), "khp_denoise_var_host")
     del keep, keep_z
     return out if ov is None else (out, ov)
+
+
+REPROJECT_OUTPUTS = {"colour": (3,), "length": (), "variance": (), "motion": (2,)}   # khp_reproject_out, in struct order
+
+
+def _reproject_args(ctx, width, height, cur, hist, out, device, params):
+    """khp_reproject_params, the two khp_reproject_frame and khp_reproject_out of a reproject call, every
+    array checked first (dtype, shape, or DeviceBuffer size) as _denoise_args checks the guides.
+    Returns (params, cur frame, hist frame or None, out struct, the outputs as a dict, keep-alives)."""
+    params = dict(params)
+    flags = int(params.pop("flags", 0)) | (N.REPROJECT_MATCH_OBJECT if params.pop("match_object", False) else 0) | \
+        (N.REPROJECT_DEVICE if device else 0)
+    for k in params:
+        if k not in dict(N.ReprojectParams._fields_) or k in ("reserved", "width", "height"):
+            raise ValueError(f"khp_reproject_params has no field {k!r} to set")
+    keep = []
+
+    def plane(name, a, tail, dtype=np.float32):
+        shape = (height, width) + tail
+        if device:
+            need = int(np.prod(shape)) * 4
+            if not isinstance(a, DeviceBuffer) or a.nbytes < need:
+                raise ValueError(f"{name}: a DeviceBuffer of {need} bytes is needed with device=True")
+            ptr = a.ptr
+        else:
+            if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != shape or not a.flags.c_contiguous:
+                raise ValueError(f"{name}: a C-contiguous {np.dtype(dtype).name} array of shape {shape} is needed")
+            ptr = a.ctypes.data
+        keep.append(a)
+        return ctypes.cast(ptr, ctypes.POINTER(ctypes.c_int32 if dtype == np.int32 else ctypes.c_float))
+
+    def frame(which, f):
+        for k in f:
+            if k not in ("camera", "colour", "variance", "length", "aov", "motion"):
+                raise ValueError(f"{which}: a frame has no entry {k!r}")
+        if not isinstance(f.get("camera"), N.Camera):
+            raise ValueError(f"{which}['camera']: an N.Camera is needed (scenes.camera makes one)")
+        s = N.ReprojectFrame(camera=f["camera"])
+        if f.get("colour") is None:
+            raise ValueError(f"{which}['colour'] is needed")
+        s.colour = plane(f"{which}['colour']", f["colour"], (3,))
+        for k in ("variance", "length"):
+            if f.get(k) is not None:
+                setattr(s, k, plane(f"{which}[{k!r}]", f[k], ()))
+        for ch, a in (f.get("aov") or {}).items():
+            if ch == "light_ended":     # the restatement's bookkeeping, not a plane
+                continue
+            if ch not in N.AOV_CHANNELS:
+                raise ValueError(f"{which}['aov']: no channel {ch!r} (one of {', '.join(N.AOV_CHANNELS)})")
+            if a is None or ch == "albedo":   # the albedo plane is never read
+                continue
+            tail, dtype = N.AOV_CHANNELS[ch]
+            setattr(s.aov, ch, plane(f"{which}['aov'][{ch!r}]", a, tail, dtype))
+        return s
+
+    cf = frame("cur", cur)
+    hf = frame("hist", hist) if hist is not None else None
+    o, res = N.ReprojectOut(), {}
+    for name, tail in REPROJECT_OUTPUTS.items():
+        if out is not None and name in out:
+            a = out[name]
+            if a is None:
+                continue
+        elif device:
+            a = DeviceBuffer(ctx, int(np.prod((height, width) + tail)) * 4)
+        else:
+            a = np.zeros((height, width) + tail, np.float32)
+        setattr(o, name, plane(f"out[{name!r}]", a, tail))
+        res[name] = a
+    if out is not None:
+        for k in out:
+            if k not in REPROJECT_OUTPUTS:
+                raise ValueError(f"out: no output {k!r} (one of {', '.join(REPROJECT_OUTPUTS)})")
+    p = N.ReprojectParams.defaults(width=width, height=height, flags=flags, **params)
+    return p, cf, hf, o, res, keep
+
+
+def reproject_host(width, height, cur: dict, hist: dict | None = None, out: dict | None = None, **params) -> dict:
+    """khp_reproject_host: HipContext.reproject as a plain host loop over the same per-pixel function --
+    no device, no context, the same bits.  numpy arrays only; returns the dict of outputs."""
+    p, cf, hf, o, res, keep = _reproject_args(None, width, height, cur, hist, out, False, params)
+    lib = N.load_library()
+    N.check(lib, lib.khp_reproject_host(ctypes.byref(p), ctypes.byref(cf), ctypes.byref(hf) if hf is not None else None,
+                                        ctypes.byref(o)), "khp_reproject_host")
+    del keep
+    return res
+
+
+class TemporalAccumulator:
+    """The ping-pong a viewer does around khp_reproject: it owns the history -- the blended
+    colour, its length and variance, and the camera and AOV planes they belong to -- and each push()
+    blends a new frame into it.  With a context the frames are DeviceBuffers of that context and the
+    kernel runs; without one they are numpy arrays and the host entry runs.  The same bits either way.
+
+        acc = TemporalAccumulator(w, h, ctx)           # **params: khp_reproject_params fields
+        shown = acc.push(cam, aov, colour)["colour"]   # every frame, moved camera or not
+        acc.reset()                                    # after set_scene: the history is of another scene
+
+    The outputs alternate between two sets of buffers: what push() returns stays as it is until the
+    push after the next.  The aov planes (and nothing else) are kept by reference as the next history's:
+    hand over planes that will not be written to before the next push."""
+
+    def __init__(self, width: int, height: int, ctx: "HipContext | None" = None, **params):
+        self.width, self.height, self.ctx, self.params = int(width), int(height), ctx, dict(params)
+        for k in params:
+            if k not in dict(N.ReprojectParams._fields_) and k != "match_object" or k in ("reserved", "width", "height", "samples"):
+                raise ValueError(f"khp_reproject_params has no field {k!r} to set here (samples goes to push())")
+        self._sets, self._turn, self._hist = [None, None], 0, None
+
+    def reset(self):
+        """Drop the history: the next push() starts one."""
+        self._hist = None
+
+    @property
+    def history(self) -> "dict | None":
+        """The frame the next push() blends into (camera, colour, length, variance, aov), or None."""
+        return self._hist
+
+    def _outputs(self):
+        if self._sets[self._turn] is None:
+            shape = lambda tail: (self.height, self.width) + tail
+            if self.ctx is not None:
+                make = lambda tail: DeviceBuffer(self.ctx, int(np.prod(shape(tail))) * 4)
+            else:
+                make = lambda tail: np.zeros(shape(tail), np.float32)
+            self._sets[self._turn] = {name: make(tail) for name, tail in REPROJECT_OUTPUTS.items()}
+        return self._sets[self._turn]
+
+    def push(self, camera: "N.Camera", aov: dict, colour, variance=None, samples: float = 1.0) -> dict:
+        """Blend the frame (camera, aov, colour, variance) of weight `samples` (its samples per pixel) into
+        the history and keep the result as the next history.  Returns the dict of khp_reproject's outputs:
+        "colour" (the frame to show, or to hand to denoise_var with "variance"), "length", "variance", "motion"."""
+        cur = {"camera": camera, "colour": colour, "variance": variance, "aov": aov}
+        out = self._outputs()
+        kw = dict(self.params, samples=samples)
+        if self.ctx is not None:
+            res = self.ctx.reproject(self.width, self.height, cur, self._hist, out=out, device=True, **kw)
+        else:
+            res = reproject_host(self.width, self.height, cur, self._hist, out=out, **kw)
+        self._turn ^= 1
+        self._hist = {"camera": camera, "colour": res["colour"], "length": res["length"], "variance": res["variance"],
+                      "aov": {ch: a for ch, a in aov.items() if ch in N.AOV_CHANNELS and ch != "albedo"}}
+        return res
 
 
 def moments_fold_host(samples: np.ndarray, first_sample: int = 0, state: dict | None = None) -> dict:

@@ -548,6 +548,95 @@ khp_status khp_denoise_var(khp_ctx* ctx, const khp_denoise_params* p, const floa
 khp_status khp_denoise_var_host(const khp_denoise_params* p, const float* colour,
                                 const khp_aov_buffers* guides, const khp_denoise_noise* noise, float* out);
 
+/* ---- temporal reprojection: carry a frame's history across a camera move --------
+ * khp_set_camera starts the running mean over.  khp_reproject instead takes the frame
+ * of the previous camera (the history: colour, its effective sample count `length`, its
+ * variance and its khp_render_aov planes) and the current camera's frame, finds for
+ * every current pixel where its first-hit point was in the history, and blends the two.
+ * The scene is static between the frames; only the camera moves.  A stateless call: the
+ * caller keeps the outputs as the next history.  One float32 function of the arguments
+ * in a fixed order of operations, the same bits from khp_reproject (a gfx950 kernel) and
+ * khp_reproject_host (a plain host loop): no atomics, nothing contracted.  The
+ * definition, operation by operation, is DESIGN.md §18; in short, per pixel (x, y)
+ *   locate   the ray through the pixel centre (x + 0.5, y + 0.5) of cur.camera as
+ *            khp_render makes it, normalised; cv = coverage; a surface pixel (cv > 0) is
+ *            the point at d = depth / cv on it, a background pixel the ray's direction,
+ *            a point at infinity (a rotation moves it, a translation does not);
+ *   project  through hist.camera (axis_x and axis_y at right angles, as khp_camera_setup
+ *            makes them) to a continuous pixel position (fx, fy); motion = (fx - (x +
+ *            0.5), fy - (y + 0.5)), or NaN, NaN where the point is not in front of the
+ *            history camera;
+ *   taps     the four bilinear taps around (fx - 0.5, fy - 0.5), dy outer and dx inner.  A
+ *            tap counts iff it is inside the image, its weight is > 0, its colour is finite,
+ *            its length is finite and > 0 and every enabled test passes: depth (both
+ *            surfaces with |d_q - dist| <= depth_tol * dist, dist the point's distance from
+ *            the history camera, or both background), normal and tangent (1 - dot of the
+ *            unit vectors <= tol; skipped when either has no length), coverage (|cv - cv_q|
+ *            <= tol), object (equal ids).  h, N, vh = the counted taps' weighted colour,
+ *            length and variance (squared weights, over the taps whose variance is known);
+ *   blend    Nc = min(N, max_history) (max_history 0: N), s = samples, alpha = s / (Nc +
+ *            s): colour h + alpha * (c - h), length Nc + s, variance (1 - alpha)^2 vh +
+ *            alpha^2 v_c.  A current pixel that is not finite takes h, Nc, vh (the history
+ *            repairs it); where no tap counted (a disocclusion, or no history) the result
+ *            is c, s, v_c; where neither is usable c as it is, length 0.
+ * A variance is the variance of the pixel's mean, channels summed, as for KHP_NOISE_PLANE;
+ * negative or not finite means unknown, and out.variance holds +inf there, so the plane
+ * feeds khp_denoise_var unchanged.  A tolerance of 0 turns its test off; a plane whose
+ * test is off is not read and may be NULL, except the current frame's depth and coverage,
+ * which locate the pixel and are always needed.  The history's coverage is read whenever
+ * depth, normal, tangent or coverage is tested.  albedo is never read.  With hist == NULL
+ * every pixel is "no tap counted", motion is NaN and no test plane is read.
+ *
+ * Each output may be NULL (not all).  out.colour == cur.colour (and out.variance ==
+ * cur.variance) is allowed: the current frame is read per pixel.  An output equal to a
+ * plane of the history is refused: the history is gathered.  khp_reproject touches no
+ * context state (framebuffer, moments, frames in flight, render-ahead, stats): it has its
+ * own staging area, is queued on the context's stream and returns when the outputs are
+ * written, like khp_denoise with a caller's colour.  KHP_REPROJECT_DEVICE: every pointer
+ * of cur, hist and out is device memory of ctx's GPU.
+ *
+ * KHP_EINVAL (checked before the context is touched, khp_last_error names the cause): a
+ * null p, cur, out or ctx; width * height == 0 or above 2^31; an unknown flag; reserved
+ * != 0; samples not finite or <= 0; max_history or a tolerance negative or NaN; every
+ * output NULL; a NULL colour; cur's depth or coverage NULL; with a history: its length
+ * NULL, an enabled test whose plane is NULL in either frame, an output that is one of
+ * its planes; KHP_REPROJECT_DEVICE at the host entry, or with a pointer that is not
+ * device memory.  KIRK has no counterpart. */
+#define KHP_REPROJECT_DEVICE       (1u << 0)  /* every plane of cur, hist and out is device memory of ctx's GPU */
+#define KHP_REPROJECT_MATCH_OBJECT (1u << 1)  /* a tap counts only if its object id is the pixel's           */
+typedef struct {
+    uint32_t width, height;   /* offset 0, 4 */
+    uint32_t flags;           /* 8: KHP_REPROJECT_* */
+    float samples;            /* 12: the current frame's weight, its samples per pixel; finite, > 0 */
+    float max_history;        /* 16: > 0: the history's length is capped at it before the blend; 0: no cap */
+    float depth_tol;          /* 20: relative; 0: the test is off */
+    float normal_tol;         /* 24: 1 - cos; 0: off */
+    float tangent_tol;        /* 28: 1 - cos; 0: off */
+    float coverage_tol;       /* 32: absolute; 0: off */
+    uint32_t reserved[3];     /* 36: 0 */
+} khp_reproject_params;       /* 48 bytes */
+typedef struct {
+    khp_camera camera;        /* offset 0: the camera the frame was rendered with */
+    uint32_t reserved;        /* 52: 0 */
+    const float* colour;      /* 56: [H][W][3] */
+    const float* variance;    /* 64: [H][W] or NULL (every variance unknown) */
+    const float* length;      /* 72: [H][W], the history frame only: the effective samples behind each pixel */
+    khp_aov_buffers aov;      /* 80: the planes khp_render_aov wrote with that camera (only read) */
+} khp_reproject_frame;        /* 128 bytes */
+typedef struct {
+    float* colour;            /* offset 0: [H][W][3] or NULL */
+    float* length;            /* 8: [H][W] or NULL */
+    float* variance;          /* 16: [H][W] or NULL; +inf where unknown */
+    float* motion;            /* 24: [H][W][2] or NULL; history position minus pixel centre, in pixels */
+} khp_reproject_out;          /* 32 bytes */
+/* 0 x 0, flags 0, samples 1, max_history 32, depth 0.05, normal 0 (off), tangent 0.25,
+ * coverage 0.5: starting values, not a measured optimum */
+void       khp_reproject_params_defaults(khp_reproject_params* out);
+khp_status khp_reproject(khp_ctx* ctx, const khp_reproject_params* p, const khp_reproject_frame* cur,
+                         const khp_reproject_frame* hist /* nullable */, const khp_reproject_out* out);
+khp_status khp_reproject_host(const khp_reproject_params* p, const khp_reproject_frame* cur,
+                              const khp_reproject_frame* hist /* nullable */, const khp_reproject_out* out);   /* no device, no context */
+
 /* ---- per-pixel sample moments: robust mean, variance, error plane --------------
  * An opt-in second accumulator beside the framebuffer.  Per pixel it holds n, the
  * count of finite samples, their mean, M2, their sum of squared deviations

@@ -224,6 +224,19 @@ class Context {
                      const khp_denoise_noise& noise, float* out) {
         check(khp_denoise_var(c_, &p, colour, &guides, &noise, out), "khp_denoise_var");
     }
+    // Carry the previous camera's frame into the current one and blend (khp_reproject): hist ==
+    // nullptr starts a history.  The outputs are the next call's history; p from reproject_defaults(w, h).
+    static khp_reproject_params reproject_defaults(uint32_t width, uint32_t height) {
+        khp_reproject_params p;
+        khp_reproject_params_defaults(&p);
+        p.width = width;
+        p.height = height;
+        return p;
+    }
+    void reproject(const khp_reproject_params& p, const khp_reproject_frame& cur, const khp_reproject_frame* hist,
+                   const khp_reproject_out& out) {
+        check(khp_reproject(c_, &p, &cur, hist, &out), "khp_reproject");
+    }
     // KHP_RENDER_ASYNC renders are complete (and accumulated in call order) after sync()
     void sync() { check(khp_sync(c_), "khp_sync"); }
     void read_framebuffer(float* out_rgb) { check(khp_read_framebuffer(c_, out_rgb), "khp_read_framebuffer"); }
