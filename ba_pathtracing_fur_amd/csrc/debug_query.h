@@ -5,7 +5,8 @@
 // light_dir, light_isect, light_emit, and (ABI 16) bsdf_sample's KINDS_LOBES
 // instance, hair_lobes.h -- so a test can compare them item by item
 // with the oracle and with a float64 reference.  ABI 17 adds the light-path
-// variant's: k_light_paths itself, bd_connection and img_connection (at the end).
+// variant's: k_light_paths itself, bd_connection and img_connection; after them come
+// the texture lookups': tex_color, env_color and hit_texcoord / resolve_material (at the end).
 // Every index is checked on the host before a launch; the kernels read nothing
 // the host has not validated.
 #pragma once
@@ -617,5 +618,146 @@ extern "C" khp_status khp_debug_img_connect(khp_ctx* c, uint32_t width, uint32_t
     HIPCHK(hipMemcpyAsync(t, ot.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(cj, oc.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     KHPCHK(wait_stream(c, c->stream, "the image-plane queries"));
+    return KHP_OK;
+}
+
+// ---- texture, environment and textured-material queries (after the ABI 15 queries) --------
+// tex_color, env_color and the hit's texcoord and resolved material, item by item; the
+// same rules as above.  The textures are in HBM only when the scene is textured (a
+// textured material parameter or an environment map), so the two that read them refuse
+// every other scene before a launch.
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_tex_color(DevScene S, uint32_t n, const int32_t* tex, const float* xy,
+                                                             float* rgba) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float4 c = tex_color(S, tex[i], xy[2 * (size_t)i], xy[2 * (size_t)i + 1]);
+        float* o = rgba + 4 * (size_t)i;
+        o[0] = c.x;
+        o[1] = c.y;
+        o[2] = c.z;
+        o[3] = c.w;
+    }
+}
+
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_env_color(DevScene S, uint32_t n, const float* dir, float* rgb) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+        st3(rgb + 3 * (size_t)i, env_color(S, ld3(dir + 3 * (size_t)i)));
+}
+
+// What k_shade does at a hit of a textured scene: trace_closest, surface_at<true> (which
+// resolves the material through textured_material), and hit_texcoord once more with the
+// arguments surface_at gave it, for the texcoord itself.  mat: 13 floats per item, diffuse,
+// specular, volume and emission rgb, then the roughness.
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_material(DevScene S, uint32_t n, const float* orig, const float* dir,
+                                                            float* t_out, int32_t* obj_out, float* bary, float* tc,
+                                                            float* mat) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const Ray r = make_ray(ld3(orig + 3 * (size_t)i), ld3(dir + 3 * (size_t)i));
+        Hit h;
+        PrivStack stk;
+        TravStats st{0, 0};
+        trace_closest<false>(S, r, h, stk, st);
+        int32_t ob = -1;
+        float bu = 0.0f, bv = 0.0f, tu = 0.0f, tv = 0.0f;
+        khp_material m;
+        const v3 zero = mk(0.0f, 0.0f, 0.0f);
+        st3(m.diffuse, zero);
+        st3(m.specular, zero);
+        st3(m.volume, zero);
+        st3(m.emission, zero);
+        m.roughness = 0.0f;
+        if (h.slot >= 0) {
+            ShadeCtx s;
+            surface_at<true>(S, r, h, s, m);
+            const Aux ax = S.aux[h.slot];
+            const float4* pr = S.prims + 4 * (size_t)h.slot;
+            if (!(ax.flags & 1u)) tri_uv(pr[0], pr[1], pr[2], r, bu, bv);
+            hit_texcoord(S, ax, pr, follow(r, h.t), s, bu, bv, tu, tv);
+            ob = (int32_t)ax.obj;
+        }
+        t_out[i] = h.t;
+        obj_out[i] = ob;
+        bary[2 * (size_t)i] = bu;
+        bary[2 * (size_t)i + 1] = bv;
+        tc[2 * (size_t)i] = tu;
+        tc[2 * (size_t)i + 1] = tv;
+        float* o = mat + 13 * (size_t)i;
+        st3(o, ld3(m.diffuse));
+        st3(o + 3, ld3(m.specular));
+        st3(o + 6, ld3(m.volume));
+        st3(o + 9, ld3(m.emission));
+        o[12] = m.roughness;
+    }
+}
+
+static khp_status dbg_textured(khp_ctx* c, const char* who) {
+    if (!c->S.textured)
+        return fail(KHP_EINVAL, std::string(who) + ": the scene has no textured material or environment map "
+                                                   "(its textures and triangle texcoords are not uploaded)");
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_debug_tex_color(khp_ctx* c, uint32_t n, const int32_t* tex, const float* xy, float* rgba) {
+    KHPCHK(dbg_enter(c, n, tex && xy && rgba));
+    KHPCHK(dbg_textured(c, "khp_debug_tex_color"));
+    for (uint32_t i = 0; i < n; ++i)
+        if (tex[i] < 0 || (size_t)tex[i] >= c->hs.tex.size())
+            return fail(KHP_EINVAL, "item " + std::to_string(i) + ": texture index out of range");
+    DevMem dt, dx, oc;
+    HIPCHK(upload(dt, tex, (size_t)n, c->stream));
+    HIPCHK(upload(dx, xy, 2 * (size_t)n, c->stream));
+    HIPCHK(oc.ensure(16 * (size_t)n));
+    hipLaunchKernelGGL(k_dbg_tex_color, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n, dt.as<int32_t>(),
+                       dx.as<float>(), oc.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rgba, oc.p, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the texture queries"));
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_debug_env_color(khp_ctx* c, uint32_t n, const float* dir, float* rgb) {
+    KHPCHK(dbg_enter(c, n, dir && rgb));
+    DevMem dd, oc;
+    HIPCHK(upload(dd, dir, 3 * (size_t)n, c->stream));
+    HIPCHK(oc.ensure(12 * (size_t)n));
+    hipLaunchKernelGGL(k_dbg_env_color, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n, dd.as<float>(),
+                       oc.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rgb, oc.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the environment queries"));
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_debug_material(khp_ctx* c, uint32_t n, const float* orig, const float* dir, float* t_out,
+                                         int32_t* obj_out, float* bary, float* texcoord, float* diffuse,
+                                         float* specular, float* volume, float* emission, float* roughness) {
+    KHPCHK(dbg_enter(c, n, orig && dir && t_out && obj_out && bary && texcoord && diffuse && specular && volume &&
+                               emission && roughness));
+    KHPCHK(dbg_textured(c, "khp_debug_material"));
+    DevMem o, d, t, ob, ba, tc, mt;
+    HIPCHK(upload(o, orig, 3 * (size_t)n, c->stream));
+    HIPCHK(upload(d, dir, 3 * (size_t)n, c->stream));
+    HIPCHK(t.ensure(4 * (size_t)n));
+    HIPCHK(ob.ensure(4 * (size_t)n));
+    HIPCHK(ba.ensure(8 * (size_t)n));
+    HIPCHK(tc.ensure(8 * (size_t)n));
+    HIPCHK(mt.ensure(52 * (size_t)n));
+    hipLaunchKernelGGL(k_dbg_material, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n, o.as<float>(),
+                       d.as<float>(), t.as<float>(), ob.as<int32_t>(), ba.as<float>(), tc.as<float>(), mt.as<float>());
+    HIPCHK(hipGetLastError());
+    std::vector<float> m(13 * (size_t)n);
+    HIPCHK(hipMemcpyAsync(t_out, t.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(obj_out, ob.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(bary, ba.p, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(texcoord, tc.p, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(m.data(), mt.p, 52 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the material queries"));
+    for (uint32_t i = 0; i < n; ++i) {
+        const float* s = &m[13 * (size_t)i];
+        memcpy(diffuse + 3 * (size_t)i, s, 12);
+        memcpy(specular + 3 * (size_t)i, s + 3, 12);
+        memcpy(volume + 3 * (size_t)i, s + 6, 12);
+        memcpy(emission + 3 * (size_t)i, s + 9, 12);
+        roughness[i] = s[12];
+    }
     return KHP_OK;
 }

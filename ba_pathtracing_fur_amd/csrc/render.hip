@@ -996,11 +996,10 @@ __global__ __launch_bounds__(256) void k_hit_scatter(Wave Wv, int cur) {
 }
 
 // Hit texcoord (Cylinder::calcTcoord, Cylinder.cpp:239-260; Triangle::calcTcoord,
-// Triangle.cpp:250-254) and the material with its textured parameters resolved.
-// m holds the material's values on entry (resolve_material overwrites the textured ones).
-__device__ __forceinline__ void textured_material(const DevScene& S, const Aux& ax, const float4* pr, v3 loc,
-                                               const ShadeCtx& s, float bu, float bv, khp_material& out) {
-    float tu, tv;
+// Triangle.cpp:250-254).  The renderer reaches it through textured_material only;
+// khp_debug_material (debug_query.h) calls it for the texcoord it returns.
+__device__ __forceinline__ void hit_texcoord(const DevScene& S, const Aux& ax, const float4* pr, v3 loc,
+                                             const ShadeCtx& s, float bu, float bv, float& tu, float& tv) {
     if (ax.flags & 1u) {
         const float4 c0 = pr[0];
         const v3 Q = loc - mk(c0.x, c0.y, c0.z);
@@ -1016,6 +1015,14 @@ __device__ __forceinline__ void textured_material(const DevScene& S, const Aux& 
         tu = (bx * tc[0] + bu * tc[2]) + bv * tc[4];
         tv = (bx * tc[1] + bu * tc[3]) + bv * tc[5];
     }
+}
+
+// The material with its textured parameters resolved at the hit's texcoord.
+// out holds the material's values on entry (resolve_material overwrites the textured ones).
+__device__ __forceinline__ void textured_material(const DevScene& S, const Aux& ax, const float4* pr, v3 loc,
+                                               const ShadeCtx& s, float bu, float bv, khp_material& out) {
+    float tu, tv;
+    hit_texcoord(S, ax, pr, loc, s, bu, bv, tu, tv);
     resolve_material(S, ax.mat, tu, tv, out);
 }
 

@@ -344,7 +344,8 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_read_moments", "khp_moments_fold_host", "khp_adaptive_defaults", "khp_render_adaptive",
             "khp_adaptive_select_host", "khp_debug_adaptive_select", "khp_debug_adaptive_list",
             "khp_denoise_noise_defaults", "khp_denoise_var", "khp_denoise_var_host",
-            "khp_reproject_params_defaults", "khp_reproject", "khp_reproject_host"]
+            "khp_reproject_params_defaults", "khp_reproject", "khp_reproject_host", "khp_debug_tex_color",
+            "khp_debug_env_color", "khp_debug_material"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
 ABI_VERSION = 17
@@ -482,6 +483,10 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
                                            P(c_float), P(c_float)]),
         "khp_debug_img_connect": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, P(c_float), P(c_uint32), P(c_float),
                                           P(c_float), P(c_uint8), P(c_float), P(c_float), P(c_float)]),
+        "khp_debug_tex_color": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_float), P(c_float)]),
+        "khp_debug_env_color": (c_int, [c_void_p, c_uint32, P(c_float), P(c_float)]),
+        "khp_debug_material": (c_int, [c_void_p, c_uint32, P(c_float), P(c_float), P(c_float), P(c_int32), P(c_float),
+                                       P(c_float), P(c_float), P(c_float), P(c_float), P(c_float), P(c_float)]),
         "khp_host_build": (c_int, [P(SceneDesc), P(c_uint32), P(c_uint32), P(c_float), P(c_int32), P(c_int32),
                                    P(c_int32), P(c_float), P(c_float)]),
     }

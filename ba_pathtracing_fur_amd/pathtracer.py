@@ -719,6 +719,39 @@ class HipContext:
             N.fptr(r["t"]), N.fptr(r["cj"])), "khp_debug_img_connect")
         return r
 
+    # ---- queries of the texture lookups (test hooks) ----
+    def debug_tex_color(self, tex, xy):
+        """khp_debug_tex_color on n (texture, x, y) items -> rgba (n, 4)."""
+        ti = np.ascontiguousarray(tex, np.int32).reshape(-1)
+        n = len(ti)
+        c = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.empty((n, 4), np.float32)
+        N.check(self.lib, self.lib.khp_debug_tex_color(self.ptr, n, ti.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                       N.fptr(c), N.fptr(out)), "khp_debug_tex_color")
+        return out
+
+    def debug_env_color(self, direction):
+        """khp_debug_env_color on n directions -> rgb (n, 3)."""
+        d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+        out = np.empty((len(d), 3), np.float32)
+        N.check(self.lib, self.lib.khp_debug_env_color(self.ptr, len(d), N.fptr(d), N.fptr(out)), "khp_debug_env_color")
+        return out
+
+    def debug_material(self, orig, direction):
+        """khp_debug_material: closest hit, its barycentrics and texcoord, and the resolved material, per ray."""
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+        n = len(o)
+        r = {"t": np.empty(n, np.float32), "obj": np.empty(n, np.int32), "bary": np.empty((n, 2), np.float32),
+             "tc": np.empty((n, 2), np.float32), "diffuse": np.empty((n, 3), np.float32),
+             "specular": np.empty((n, 3), np.float32), "volume": np.empty((n, 3), np.float32),
+             "emission": np.empty((n, 3), np.float32), "roughness": np.empty(n, np.float32)}
+        N.check(self.lib, self.lib.khp_debug_material(
+            self.ptr, n, N.fptr(o), N.fptr(d), N.fptr(r["t"]), r["obj"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            N.fptr(r["bary"]), N.fptr(r["tc"]), N.fptr(r["diffuse"]), N.fptr(r["specular"]), N.fptr(r["volume"]),
+            N.fptr(r["emission"]), N.fptr(r["roughness"])), "khp_debug_material")
+        return r
+
     def debug_queues(self):
         """The extension rays and the shadow rays (o, d, t_max) of bounce
         khp_ctx_params.dump_bounce of the last synchronous render."""

@@ -1109,6 +1109,29 @@ khp_status khp_debug_bdpt_connect(khp_ctx* ctx, uint32_t n, const float* orig, c
 khp_status khp_debug_img_connect(khp_ctx* ctx, uint32_t width, uint32_t height, uint32_t n, const float* sensor,
                                  const uint32_t* j, const float* prev, const float* cur, uint8_t* accepted,
                                  float* dir, float* t, float* cj);
+/* ---- queries of the texture lookups (test hooks, additive) -------
+ * Same rules as the ABI 15 queries: one item per thread, the device functions
+ * the renderer calls, n in [1, 2^20], no null array, a built scene, every index
+ * checked on the host (KHP_EINVAL naming the first bad item, nothing launched),
+ * scratch of their own -- context, framebuffer and statistics untouched.
+ *
+ * khp_debug_tex_color: Texture::getColor of texture tex[i] (index into the
+ * scene's textures) at xy[i] ([n][2]) -> rgba [n][4].  The textures are on the
+ * device only for a scene with a textured material parameter or an environment
+ * map; any other scene is KHP_EINVAL. */
+khp_status khp_debug_tex_color(khp_ctx* ctx, uint32_t n, const int32_t* tex, const float* xy, float* rgba);
+/* Environment::getColor for the direction dir[i] ([n][3], normalised as
+ * KIRK does) -> rgb [n][3]. */
+khp_status khp_debug_env_color(khp_ctx* ctx, uint32_t n, const float* dir, float* rgb);
+/* The closest hit of ray i (as khp_debug_surface) and what the shader reads
+ * there: t ([n], FLT_MAX on a miss), object id (-1), the hit's barycentrics
+ * [n][2] (u, v; zero for cones), calcTcoord's texcoord [n][2], and the material
+ * with its textured parameters resolved: diffuse, specular, volume, emission
+ * ([n][3] each) and roughness [n].  A miss leaves all of these zero.  A scene
+ * without textures is KHP_EINVAL (no triangle texcoords on the device). */
+khp_status khp_debug_material(khp_ctx* ctx, uint32_t n, const float* orig, const float* dir, float* t,
+                              int32_t* object, float* barycentrics, float* texcoord, float* diffuse,
+                              float* specular, float* volume, float* emission, float* roughness);
 /* ABI 13, test hook for the bounded device waits of a rank: builds
  * one RCCL-operation bracket (events `pre` / `post`, as around an ncclSend /
  * ncclRecv) on the context stream around a gate kernel that spins until

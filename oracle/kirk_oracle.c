@@ -2221,6 +2221,46 @@ int ko_surface(ko_ctx* c, uint32_t n, const float* orig, const float* dir, float
     return KHP_OK;
 }
 
+/* Counterpart of khp_debug_material: the closest hit of n rays, its barycentrics,
+ * calcTcoord and the material with its textured parameters fetched there (obj_tcoord,
+ * material_at, as the renders call them).  A miss leaves the item zero (t FLT_MAX,
+ * object -1); a scene without textures returns KHP_EINVAL. */
+int ko_debug_material(ko_ctx* c, uint32_t n, const float* orig, const float* dir, float* t_out, int32_t* obj_out,
+                      float* bary, float* tc, float* diffuse, float* specular, float* volume, float* emission,
+                      float* roughness) {
+    if (!c || !(c->textured || c->env_map.type != KHP_ENV_COLOR)) return KHP_EINVAL;   /* the device's "textured" */
+    for (uint32_t i = 0; i < n; ++i) {
+        ray_t r = make_ray(ld3(orig + 3 * (size_t)i), ld3(dir + 3 * (size_t)i));
+        hit_t h;
+        bvh_closest(c, &r, &h, NULL);
+        t_out[i] = h.lambda;
+        obj_out[i] = h.obj;
+        memset(bary + 2 * (size_t)i, 0, 2 * sizeof(float));
+        memset(tc + 2 * (size_t)i, 0, 2 * sizeof(float));
+        memset(diffuse + 3 * (size_t)i, 0, 3 * sizeof(float));
+        memset(specular + 3 * (size_t)i, 0, 3 * sizeof(float));
+        memset(volume + 3 * (size_t)i, 0, 3 * sizeof(float));
+        memset(emission + 3 * (size_t)i, 0, 3 * sizeof(float));
+        roughness[i] = 0.0f;
+        if (h.obj < 0) continue;
+        const obj_t* o = &c->obj[h.obj];
+        float tu, tv;
+        khp_material m;
+        obj_tcoord(o, &h, follow(&r, h.lambda), &tu, &tv);
+        material_at(c, o->mat, tu, tv, &m);
+        bary[2 * (size_t)i] = h.bu;
+        bary[2 * (size_t)i + 1] = h.bv;
+        tc[2 * (size_t)i] = tu;
+        tc[2 * (size_t)i + 1] = tv;
+        memcpy(diffuse + 3 * (size_t)i, m.diffuse, 3 * sizeof(float));
+        memcpy(specular + 3 * (size_t)i, m.specular, 3 * sizeof(float));
+        memcpy(volume + 3 * (size_t)i, m.volume, 3 * sizeof(float));
+        memcpy(emission + 3 * (size_t)i, m.emission, 3 * sizeof(float));
+        roughness[i] = m.roughness;
+    }
+    return KHP_OK;
+}
+
 /* calcLightdir (randomize = true) of light li[i] from point p[i] with draws u[i]. */
 int ko_light_dir(ko_ctx* c, uint32_t n, const int32_t* li, const float* p, const float* u, float* ro, float* rd,
                  float* att) {

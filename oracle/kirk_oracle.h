@@ -109,6 +109,11 @@ int ko_surface(ko_ctx* c, uint32_t n, const float* orig, const float* dir, float
                float* nrm, float* uvw, int32_t* mat);
 int ko_light_dir(ko_ctx* c, uint32_t n, const int32_t* li, const float* p, const float* u, float* ro, float* rd,
                  float* att);
+/* Counterpart of khp_debug_material (khp_debug_tex_color's and khp_debug_env_color's are
+ * ko_tex_color and ko_env_color): the same arguments and outputs. */
+int ko_debug_material(ko_ctx* c, uint32_t n, const float* orig, const float* dir, float* t_out, int32_t* obj_out,
+                      float* bary, float* tc, float* diffuse, float* specular, float* volume, float* emission,
+                      float* roughness);
 int ko_light_isect(ko_ctx* c, uint32_t n, const int32_t* li, const float* orig, const float* dir, uint8_t* hit,
                    float* t_out, float* emit);
 

@@ -81,6 +81,8 @@ def load():
                                P(c_float), P(c_int32)]),
         "ko_light_dir": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_float), P(c_float), P(c_float), P(c_float),
                                  P(c_float)]),
+        "ko_debug_material": (c_int, [c_void_p, c_uint32, P(c_float), P(c_float), P(c_float), P(c_int32), P(c_float),
+                                      P(c_float), P(c_float), P(c_float), P(c_float), P(c_float), P(c_float)]),
         "ko_light_isect": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_float), P(c_float), P(c_uint8), P(c_float),
                                    P(c_float)]),
         "ko_bdpt_connect_n": (c_int, [c_void_p, c_uint32, P(c_float), P(c_float), P(c_uint32), P(c_int32), P(c_uint32),
@@ -241,6 +243,36 @@ class Oracle:
                                  _ip(r["mat"]))
         if rc != 0:
             raise ValueError(f"ko_surface failed ({rc})")
+        return r
+
+    def debug_tex_color(self, tex, xy):
+        """Counterpart of HipContext.debug_tex_color: (texture, x, y) items -> rgba (n, 4)."""
+        ti = np.ascontiguousarray(tex, np.int32).reshape(-1)
+        c = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        if ti.min() < 0 or ti.max() >= len(self.scene.textures):
+            raise ValueError("texture index out of range")
+        out = np.empty((len(ti), 4), np.float32)
+        for i in range(len(ti)):
+            self.lib.ko_tex_color(self.ptr, int(ti[i]), float(c[i, 0]), float(c[i, 1]), _fp(out[i]))
+        return out
+
+    def debug_env_color(self, direction):
+        return self.env_color(direction)
+
+    def debug_material(self, orig, direction):
+        """Counterpart of HipContext.debug_material: the same keys."""
+        o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+        n = len(o)
+        r = {"t": np.empty(n, np.float32), "obj": np.empty(n, np.int32), "bary": np.empty((n, 2), np.float32),
+             "tc": np.empty((n, 2), np.float32), "diffuse": np.empty((n, 3), np.float32),
+             "specular": np.empty((n, 3), np.float32), "volume": np.empty((n, 3), np.float32),
+             "emission": np.empty((n, 3), np.float32), "roughness": np.empty(n, np.float32)}
+        rc = self.lib.ko_debug_material(self.ptr, n, _fp(o), _fp(d), _fp(r["t"]), _ip(r["obj"]), _fp(r["bary"]),
+                                        _fp(r["tc"]), _fp(r["diffuse"]), _fp(r["specular"]), _fp(r["volume"]),
+                                        _fp(r["emission"]), _fp(r["roughness"]))
+        if rc != 0:
+            raise ValueError(f"ko_debug_material failed ({rc})")
         return r
 
     def debug_bsdf_sample(self, obj, mat, ray_in, normal, sample, hair, flags_in, kinds_mask=None):

@@ -62,9 +62,11 @@ def albedo_table(sd):
     return tab
 
 
-def sample_records(ctx, sd, o, raw):
+def sample_records(ctx, sd, o, raw, albedo=None):
     """The definition's per-sample record for rays (o, raw): dict of float columns, `object`, and
-    `light_ended` (a hit that a nearer light takes: not a surface sample)."""
+    `light_ended` (a hit that a nearer light takes: not a surface sample).  albedo: the resolved
+    diffuse of every ray's hit (n, 3), for textures that are not one colour (khp_debug_material's
+    answer); without it albedo_table's."""
     n = len(o)
     hit = ctx.debug_surface(o, raw)
     t_lights = np.full(n, FLT_MAX, F32)
@@ -76,7 +78,7 @@ def sample_records(ctx, sd, o, raw):
     with np.errstate(invalid="ignore"):
         surf = has & ~(t_lights < hit["t"])
     zero3 = np.zeros((n, 3), F32)
-    alb = albedo_table(sd)[np.where(surf, hit["mat"], 0)]
+    alb = albedo_table(sd)[np.where(surf, hit["mat"], 0)] if albedo is None else np.asarray(albedo, F32)
     return {"normal": np.where(surf[:, None], hit["n"], zero3),
             "albedo": np.where(surf[:, None], alb, zero3),
             "tangent": np.where(surf[:, None], hit["uvw"][:, 1], zero3),

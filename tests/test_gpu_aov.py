@@ -165,6 +165,36 @@ def test_constant_textures_match_and_give_the_known_albedo():
     assert plain.any() and np.array_equal(got["albedo"][plain], np.tile(F32([0.1, 0.7, 0.3]), (int(plain.sum()), 1)))
 
 
+def test_albedo_of_real_textures_is_the_material_query():
+    """Textures whose texel depends on the hit (test_texture_truth's hit scene: every channel count, the
+    pow wrap, uv beyond [0, 1], fibres in world space and under a node transform): the albedo of a sample
+    is khp_debug_material's resolved diffuse for the restated camera ray -- the query test_texture_truth
+    pins to a float64 truth -- and a pixel's albedo the ordered float32 mean of its samples'."""
+    from test_texture_truth import hit_scene
+    sd = hit_scene(W, H)
+    npix = W * H
+    with Ctx(sd) as c:
+        for spp, first in ((1, 0), (3, 2)):
+            pixels = np.repeat(np.arange(npix, dtype=np.uint64), spp)
+            samples = np.tile(np.arange(first, first + spp, dtype=np.uint64), npix)
+            o, raw, _ = A.camera_rays(sd.cam, W, pixels, SEEDS[1], samples)
+            q = c.debug_material(o, raw)
+            rec = A.sample_records(c, sd, o, raw, albedo=q["diffuse"])
+            assert np.array_equal(rec["object"], np.where(rec["coverage"] == 1, q["obj"], -1))
+            want = {ch: a.reshape((H, W) + a.shape[1:]) for ch, a in A.reduce_records(rec, npix, spp).items()}
+            got = c.render_aov(W, H, spp, seed=SEEDS[1], first_sample=first)
+            check(got, want, f"spp {spp}")
+            if spp == 1:        # wherever the one sample is a surface sample: the query's own answers, bit for bit
+                full = got["coverage"].reshape(-1) == 1.0
+                assert full.mean() > 0.5
+                assert np.array_equal(A.bits(got["albedo"].reshape(-1, 3)[full]), A.bits(q["diffuse"][full]))
+                assert np.array_equal(got["object"].reshape(-1)[full], q["obj"][full])
+                assert np.array_equal(A.bits(got["depth"].reshape(-1)[full]), A.bits(q["t"][full]))
+                # and the texel does depend on the hit: the floor alone shows many colours
+                floor = full & (q["obj"] >= 0) & (q["obj"] < 2)
+                assert len(np.unique(got["albedo"].reshape(-1, 3)[floor], axis=0)) > 8
+
+
 def test_samples_that_end_on_a_light_are_not_surface_samples():
     sd = one_cone_scene()
     got, want = _scene_case(sd, spp=4)

@@ -235,6 +235,55 @@ def test_quirk_scenes(hip_ctx, name, path_kernel):
         hip_ctx.set_params(**old)
 
 
+def _unreached_texture_modes_scene(w, h):
+    """What scenes.textured leaves out: a floor with a wrap-mode-2 (pow) diffuse texture and uv beyond
+    [0, 1], a 2-channel diffuse, a 1-channel specular, a 1 x 1 emission texture, and the sphere map."""
+    rng = np.random.default_rng(7001)
+    sd = S.SceneData(name="unreached_texture_modes")
+    tex = lambda tw, th, ch, wrap=N.TEX_WRAP_TILE: sd.add_texture(rng.integers(0, 256, (th, tw, ch), dtype=np.uint8), wrap)
+    floor = sd.add_material(S.material(diffuse=(0.5, 0.5, 0.5)))
+    sd.set_material_texture(floor, "diffuse", tex(13, 7, 3, 2))
+    v, n = S.quad((-4, 0, -4), (-4, 0, 4), (4, 0, 4), (4, 0, -4), (0, 1, 0))
+    sd.add_triangles(v, n, floor, uv=np.float32([[[-1.5, -1.5], [-1.5, 2.5], [2.5, 2.5]],
+                                                 [[-1.5, -1.5], [2.5, 2.5], [2.5, -1.5]]]))
+    two = sd.add_material(S.material(diffuse=(0.2, 0.3, 0.6)))
+    sd.set_material_texture(two, "diffuse", tex(9, 5, 2))
+    v, n = S.quad((-1.8, 0, -1.5), (0.2, 0, -1.5), (0.2, 1.6, -1.5), (-1.8, 1.6, -1.5), (0, 0, 1))
+    sd.add_triangles(v, n, two, uv=np.float32([[[0, 0], [1, 0], [1, 1]], [[0, 0], [1, 1], [0, 1]]]))
+    glossy = sd.add_material(S.material("GlossyBSDF", diffuse=(0.3, 0.3, 0.3), roughness=0.3))
+    sd.set_material_texture(glossy, "specular", tex(7, 7, 1))
+    gv, gn = S.icosphere(2, (1.3, 0.4, 0.3), 0.4)
+    uv = np.stack([0.5 + 0.5 * np.arctan2(gv[..., 2] - 0.3, gv[..., 0] - 1.3) / np.pi, gv[..., 1] / 0.8],
+                  axis=-1).astype(np.float32)
+    sd.add_triangles(gv, gn, glossy, uv=uv)
+    emit = sd.add_material(S.material("EmissionBSDF", emission=(1.0, 1.0, 1.0)))
+    sd.set_material_texture(emit, "emission", sd.add_texture(np.uint8([[[255, 180, 90]]])))
+    v, n = S.quad((0.6, 0.9, -1.4), (1.8, 0.9, -1.4), (1.8, 1.7, -1.4), (0.6, 1.7, -1.4), (0, 0, 1))
+    sd.add_triangles(v, n, emit, uv=np.float32([[[0, 0], [1, 0], [1, 1]], [[0, 0], [1, 1], [0, 1]]]))
+    sd.lights.append(S.quad_light((0.0, 2.8, 0.0), (0.0, -1.0, 0.0), (1.2, 1.2), (4.0, 4.0, 4.0), att_const=1.0))
+    sd.set_environment_map(N.ENV_SPHERE_MAP, [tex(16, 16, 3)])
+    sd.env_ambient = (0.05, 0.05, 0.05)
+    sd.cam = S.camera((0.0, 1.3, 3.4), (0.0, -0.25, -1.0), (0.0, 1.0, 0.0), w, h)
+    return sd
+
+
+@pytest.mark.parametrize("path_kernel", [1, 2])
+def test_unreached_texture_modes_frame(hip_ctx, path_kernel):
+    """One frame through the lookups no other frame reaches (tests/test_texture_truth.py pins them item by
+    item; this is the render path's use of them), bit for bit through both kernels."""
+    w, h = 48, 32
+    sd = _unreached_texture_modes_scene(w, h)
+    want = oracle_ffi.Oracle(sd).render(w, h, 2, 4, threads=16)
+    hip_ctx.set_scene(sd)
+    hip_ctx.build_accel()
+    old = hip_ctx.set_params(path_kernel=path_kernel)
+    try:
+        assert_parity(hip_ctx.render(w, h, 2, 4), want, exact=True)
+    finally:
+        hip_ctx.set_params(**old)
+    assert len(np.unique(want.reshape(-1, 3), axis=0)) > w * h // 4       # a frame with content
+
+
 @pytest.mark.parametrize("trace_kernels", [0, 1, 2])
 @pytest.mark.parametrize("n_extra", [0, 64])
 def test_equal_t_within_a_leaf(hip_ctx, n_extra, trace_kernels):
