@@ -28,6 +28,7 @@
 
 #include "device_build.h"
 #include "scene.h"
+#include "split_rule.h"
 
 namespace khp {
 namespace gb {
@@ -43,7 +44,7 @@ struct GNode {  // interior node of the level phase
     uint32_t first, count, lturns, depth;
     int32_t axis, plane;
     float k, cbmin;
-    uint32_t L, chunk0, nchunk, bad;
+    uint32_t L, chunk0, nchunk, bad;  // bad: 1 = refused (error), 2 = no plane found, the node is a leaf
 };
 struct SRoot {  // root of a subtree finished by one thread
     float cb[6];
@@ -80,6 +81,8 @@ KHD float area(const GBox& b) {
 KHD bool worth(const GBox& b) {
     return b.mx[0] - b.mn[0] > 0.0f && b.mx[1] - b.mn[1] > 0.0f && b.mx[2] - b.mn[2] > 0.0f;
 }
+// worthSplitting() and a defined split (split_rule.h): the node is split, unless the sweep finds no plane
+KHD bool splittable(const GBox& b) { return worth(b) && split_defined(b.mn, b.mx); }
 KHD float split_k(float cbmin, float cbmax) {
     const float cbdiff = cbmax - cbmin;
     const float epsilon = 0.1f;
@@ -196,7 +199,7 @@ __global__ __launch_bounds__(256) void k_bin(const float4* __restrict__ rec, con
 __device__ void spawn(uint32_t first, uint32_t count, const GBox& cb, uint32_t lturns, uint32_t depth, GNode* g,
                       uint32_t gcap, SRoot* sr, uint32_t scap, LLeaf* ll, uint32_t lcap, uint32_t* leafstart, Ctr* ct) {
     atomicMax(&ct->max_depth, depth);
-    if (count - 1u > 1u && worth(cb)) {
+    if (count - 1u > 1u && splittable(cb)) {
         if (count <= SMALL) {
             const uint32_t s = atomicAdd(&ct->n_sroot, 1u);
             if (s >= scap) { atomicOr(&ct->error, 1u); return; }
@@ -332,7 +335,17 @@ __global__ __launch_bounds__(PICK_GROUPS * BW) void k_pick(GNode* g, uint32_t b,
     nd.cbmin = nd.cb[best_axis];
     nd.k = split_k(nd.cb[best_axis], nd.cb[3 + best_axis]);
     nd.L = bestL;
-    if (bestL == 0 || bestL >= nd.count) {  // cannot happen for worth(cb) boxes; refuse rather than loop
+    if (!cost_defined(best)) {  // no plane below FLT_MAX: a leaf (split_rule.h); the later kernels skip it
+        nd.bad = 2;
+        g[i] = nd;
+        const uint32_t s = atomicAdd(&ct->n_lleaf, 1u);
+        if (s >= lcap) { atomicOr(&ct->error, 4u); return; }
+        ll[s] = LLeaf{nd.first, nd.count, nd.lturns, nd.depth};
+        leafstart[nd.first] = 1u;
+        atomicMax(&ct->max_leaf, nd.count);
+        return;
+    }
+    if (bestL == 0 || bestL >= nd.count) {  // cannot happen for a defined split; refuse rather than loop
         nd.bad = 1;
         atomicOr(&ct->error, 8u);
     }
@@ -547,7 +560,8 @@ __global__ __launch_bounds__(64) void k_subtree(float4* rec, const float* __rest
             maxd = max(maxd, f.depth);
             const GBox cb = cb_of(f.cb);
             const uint32_t c = f.second - f.first + 1;
-            if (c - 1u > 1u && worth(cb)) {
+            bool leaf = !(c - 1u > 1u && splittable(cb));  // wave-uniform
+            if (!leaf) {
                 float k[3], cbmin[3];
                 for (int a = 0; a < 3; ++a) {
                     cbmin[a] = cb.mn[a];
@@ -641,71 +655,71 @@ __global__ __launch_bounds__(64) void k_subtree(float4* rec, const float* __rest
                     cb_put(s_rcb[0], rb1);
                 }
                 __syncthreads();
-                if (L == 0 || L >= c) {  // cannot happen for worth(cb) boxes; refuse rather than loop
-                    if (lane == 0) atomicOr(&ct->error, 32u);
-                    failed = true;
-                    break;
-                }
-                const uint32_t mid = f.first + L;
+                leaf = !found;  // no plane below FLT_MAX: a leaf (split_rule.h)
+                if (!leaf) {
+                    if (L == 0 || L >= c) {  // cannot happen for a defined split; refuse rather than loop
+                        if (lane == 0) atomicOr(&ct->error, 32u);
+                        failed = true;
+                        break;
+                    }
+                    const uint32_t mid = f.first + L;
 #ifdef KHP_BUILD_DEBUG
-                if (lane == 0) printf("  split ax %d plane %d L %u cost %g\n", ax, plane, L, bc);
+                    if (lane == 0) printf("  split ax %d plane %d L %u cost %g\n", ax, plane, L, bc);
 #endif
-                uint32_t mL = 0, mR = 0;
-                for (uint32_t r0 = f.first; r0 <= f.second; r0 += 64) {
-                    const uint32_t i = r0 + lane;
-                    bool fl = false, fr = false;
-                    if (i <= f.second) {
-                        const float4 e = srec[i];
-                        const float cc = ax == 0 ? e.x : (ax == 1 ? e.y : e.z);
-                        const bool rs = (int)(k[ax] * (cc - cbmin[ax])) > plane;
-                        fl = i < mid && rs;
-                        fr = i >= mid && !rs;
+                    uint32_t mL = 0, mR = 0;
+                    for (uint32_t r0 = f.first; r0 <= f.second; r0 += 64) {
+                        const uint32_t i = r0 + lane;
+                        bool fl = false, fr = false;
+                        if (i <= f.second) {
+                            const float4 e = srec[i];
+                            const float cc = ax == 0 ? e.x : (ax == 1 ? e.y : e.z);
+                            const bool rs = (int)(k[ax] * (cc - cbmin[ax])) > plane;
+                            fl = i < mid && rs;
+                            fr = i >= mid && !rs;
+                        }
+                        const uint64_t bl = __ballot(fl), br = __ballot(fr);
+                        if (fl) PL[mL + lane_rank(bl)] = i;
+                        if (fr) PR[mR + lane_rank(br)] = i;
+                        mL += (uint32_t)__popcll(bl);
+                        mR += (uint32_t)__popcll(br);
                     }
-                    const uint64_t bl = __ballot(fl), br = __ballot(fr);
-                    if (fl) PL[mL + lane_rank(bl)] = i;
-                    if (fr) PR[mR + lane_rank(br)] = i;
-                    mL += (uint32_t)__popcll(bl);
-                    mR += (uint32_t)__popcll(br);
-                }
-                __syncthreads();
-                // k-th misplaced of the left region <-> k-th misplaced of the right region from its end
-                for (uint32_t q = lane; q < mL; q += 64) {
-                    const uint32_t pa = PL[q], pb = PR[mR - 1u - q];
-                    const float4 ta = srec[pa];
-                    srec[pa] = srec[pb];
-                    srec[pb] = ta;
-                    for (int z = 0; z < 6; ++z) {
-                        const float tz = sb[z][pa];
-                        sb[z][pa] = sb[z][pb];
-                        sb[z][pb] = tz;
+                    __syncthreads();
+                    // k-th misplaced of the left region <-> k-th misplaced of the right region from its end
+                    for (uint32_t q = lane; q < mL; q += 64) {
+                        const uint32_t pa = PL[q], pb = PR[mR - 1u - q];
+                        const float4 ta = srec[pa];
+                        srec[pa] = srec[pb];
+                        srec[pb] = ta;
+                        for (int z = 0; z < 6; ++z) {
+                            const float tz = sb[z][pa];
+                            sb[z][pa] = sb[z][pb];
+                            sb[z][pb] = tz;
+                        }
                     }
+                    if (lane == 0) {
+                        node.count = 0;
+                        out[ni] = node;
+                    }
+                    if (sp + 2 > SUB_STACK) {
+                        if (lane == 0) atomicOr(&ct->error, 16u);
+                        failed = true;
+                        break;
+                    }
+                    const GBox lcb = cb_of(s_lcb[0]), rcb = cb_of(s_rcb[0]);
+                    if (lane == 0) {
+                        Frame r{};
+                        cb_put(r.cb, rcb);
+                        r.first = mid; r.second = f.second; r.depth = f.depth + 1; r.parent = ni; r.side = 1;
+                        stk[sp] = r;
+                        Frame l{};
+                        cb_put(l.cb, lcb);
+                        l.first = f.first; l.second = mid - 1; l.depth = f.depth + 1; l.parent = ni; l.side = 0;
+                        stk[sp + 1] = l;
+                    }
+                    sp += 2;
                 }
-                if (lane == 0) {
-                    node.count = 0;
-                    out[ni] = node;
-                }
-                if (sp + 2 > SUB_STACK) {
-                    if (lane == 0) atomicOr(&ct->error, 16u);
-                    failed = true;
-                    break;
-                }
-                GBox lcb = box_empty(), rcb = box_empty();
-                if (found) {
-                    lcb = cb_of(s_lcb[0]);
-                    rcb = cb_of(s_rcb[0]);
-                }
-                if (lane == 0) {
-                    Frame r{};
-                    cb_put(r.cb, rcb);
-                    r.first = mid; r.second = f.second; r.depth = f.depth + 1; r.parent = ni; r.side = 1;
-                    stk[sp] = r;
-                    Frame l{};
-                    cb_put(l.cb, lcb);
-                    l.first = f.first; l.second = mid - 1; l.depth = f.depth + 1; l.parent = ni; l.side = 0;
-                    stk[sp + 1] = l;
-                }
-                sp += 2;
-            } else {
+            }
+            if (leaf) {
                 node.first = (int32_t)(base + f.first);
                 node.count = (int32_t)c;
                 node.left = node.right = -1;
@@ -768,6 +782,7 @@ __global__ void k_level_interior(const GNode* g, uint32_t b, uint32_t n, const u
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const GNode nd = g[b + i];
+    if (nd.bad) return;  // became a leaf (k_level_leaves wrote it)
     const int32_t pre = (int32_t)(nd.lturns + 2u * P[nd.first]);
     const int32_t l = pre + 1;
     const int32_t r = pre + 2 * (int32_t)(P[nd.first + nd.L] - P[nd.first]);
@@ -885,7 +900,7 @@ std::string device_build_bvh(HostScene& hs, const DeviceObjects& o, hipStream_t 
     GBCHK(ctr.ensure(sizeof(Ctr)));
     Ctr hc{};
     // the root: KIRK's split() on (0, N-1) with the centroid box of everything
-    const bool root_split = (N - 1u > 1u) && worth(rootcb);
+    const bool root_split = (N - 1u > 1u) && splittable(rootcb);
     if (root_split && N > SMALL) {
         GNode r{};
         cb_put(r.cb, rootcb);

@@ -15,6 +15,14 @@
 namespace khp {
 namespace fl {
 
+// x - x is 0 for a finite x and NaN for an infinity or a NaN: a sum of such terms is 0 only if all are finite
+__device__ __forceinline__ bool all_finite(v3 a, v3 b, v3 c) {
+    const v3 d = ((a - a) + (b - b)) + (c - c);
+    return (d.x + d.y) + d.z == 0.0f;
+}
+
+// err bits: 1 triangle material, 2 cone material, 4 cone model, 8 tri_v, 16 cone_base_r0,
+// 32 cone_apex_r1 not finite, 64 finite geometry whose box or centroid overflows float32
 __global__ void k_flatten_tris(const float* __restrict__ tv, const float* __restrict__ tn,
                                const uint32_t* __restrict__ tm, const float* __restrict__ uv_in, uint32_t n_tris,
                                uint32_t n_mat, float4* rec, Aux* aux, float* bounds, float* cen, float* nrm,
@@ -23,10 +31,11 @@ __global__ void k_flatten_tris(const float* __restrict__ tv, const float* __rest
     if (i >= n_tris) return;
     const float* v = tv + 9 * (size_t)i;
     const float* n = tn + 9 * (size_t)i;
-    float r[16];
-    tri_object(ld3(v), ld3(v + 3), ld3(v + 6), ld3(n), ld3(n + 3), ld3(n + 6), r, bounds + 6 * (size_t)i,
-               cen + 3 * (size_t)i, nrm + 9 * (size_t)i, uv_in ? uv_in + 6 * (size_t)i : nullptr,
-               uv_out ? uv_out + 6 * (size_t)i : nullptr);
+    float r[16], bnd[6], ce[3];  // box and centroid stay in registers for the overflow check
+    tri_object(ld3(v), ld3(v + 3), ld3(v + 6), ld3(n), ld3(n + 3), ld3(n + 6), r, bnd, ce, nrm + 9 * (size_t)i,
+               uv_in ? uv_in + 6 * (size_t)i : nullptr, uv_out ? uv_out + 6 * (size_t)i : nullptr);
+    for (int q = 0; q < 6; ++q) bounds[6 * (size_t)i + q] = bnd[q];
+    for (int q = 0; q < 3; ++q) cen[3 * (size_t)i + q] = ce[q];
     float4* o = rec + 4 * (size_t)i;
     o[0] = make_float4(r[0], r[1], r[2], r[3]);
     o[1] = make_float4(r[4], r[5], r[6], r[7]);
@@ -34,6 +43,8 @@ __global__ void k_flatten_tris(const float* __restrict__ tv, const float* __rest
     o[3] = make_float4(r[12], r[13], r[14], r[15]);
     const uint32_t m = tm[i];
     if (m >= n_mat) atomicOr(err, 1u);
+    if (!all_finite(ld3(v), ld3(v + 3), ld3(v + 6))) atomicOr(err, 8u);
+    else if (!all_finite(ld3(bnd), ld3(bnd + 3), ld3(ce))) atomicOr(err, 64u);
     aux[i] = Aux{0.0f, m, i, 0u};
 }
 
@@ -48,7 +59,7 @@ __global__ void k_flatten_cones(const float4* __restrict__ b, const float4* __re
     const uint32_t id = id0 + i;
     const float4 bb = b[i], aa = a[i];
     const v3 base = mk(bb.x, bb.y, bb.z), apex = mk(aa.x, aa.y, aa.z);
-    float r[16];
+    float r[16], bnd[6], ce[3];  // box and centroid stay in registers for the overflow check
     float base_d;
     if (models) {
         uint32_t k = cmod ? cmod[i] : 0u;
@@ -57,10 +68,12 @@ __global__ void k_flatten_cones(const float4* __restrict__ b, const float4* __re
             k = 0;
         }
         const float* M = models + 25 * (size_t)k;
-        base_d = cone_object_xf(base, apex, bb.w, aa.w, M, M + 16, r, bounds + 6 * (size_t)id, cen + 3 * (size_t)id);
+        base_d = cone_object_xf(base, apex, bb.w, aa.w, M, M + 16, r, bnd, ce);
     } else {
-        base_d = cone_object(base, apex, bb.w, aa.w, r, bounds + 6 * (size_t)id, cen + 3 * (size_t)id);
+        base_d = cone_object(base, apex, bb.w, aa.w, r, bnd, ce);
     }
+    for (int q = 0; q < 6; ++q) bounds[6 * (size_t)id + q] = bnd[q];
+    for (int q = 0; q < 3; ++q) cen[3 * (size_t)id + q] = ce[q];
     if (cone_h) cone_h[i] = length(apex - base);  // Cylinder::m_height (pre-transform)
     float4* o = rec + 4 * (size_t)id;
     o[0] = make_float4(r[0], r[1], r[2], r[3]);
@@ -69,6 +82,11 @@ __global__ void k_flatten_cones(const float4* __restrict__ b, const float4* __re
     o[3] = make_float4(r[12], r[13], r[14], r[15]);
     const uint32_t m = cm[i];
     if (m >= n_mat) atomicOr(err, 2u);
+    const bool base_ok = all_finite(base, mk(bb.w, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f));
+    const bool apex_ok = all_finite(apex, mk(aa.w, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f));
+    if (!base_ok) atomicOr(err, 16u);
+    if (!apex_ok) atomicOr(err, 32u);
+    if (base_ok && apex_ok && !all_finite(ld3(bnd), ld3(bnd + 3), ld3(ce))) atomicOr(err, 64u);
     aux[id] = Aux{base_d, m, id, 1u};
 }
 
@@ -269,6 +287,10 @@ std::string device_flatten(const khp_scene* s, bool device_ptrs, uint32_t n_mate
     if (herr & 1u) return "EINVAL:triangle material index out of range";
     if (herr & 2u) return "EINVAL:cone material index out of range";
     if (herr & 4u) return "EINVAL:cone model index out of range";
+    if (herr & 8u) return "EINVAL:tri_v holds a NaN or an infinity";
+    if (herr & 16u) return "EINVAL:cone_base_r0 holds a NaN or an infinity";
+    if (herr & 32u) return "EINVAL:cone_apex_r1 holds a NaN or an infinity";
+    if (herr & 64u) return "EINVAL:an object's bounds or centroid overflow float32";
     return std::string();
 }
 

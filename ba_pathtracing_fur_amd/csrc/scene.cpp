@@ -5,6 +5,7 @@
 // documented semantics bit-for-bit.
 #include "scene.h"
 #include "objects.h"
+#include "split_rule.h"
 
 #include <string.h>
 
@@ -184,6 +185,15 @@ std::string flatten_scene(const khp_scene* s, HostScene& hs, bool objects) {
     if (s->cone_model)
         for (uint32_t i = 0; i < s->n_cones; ++i)
             if (s->cone_model[i] >= s->n_cone_models) return "cone model index out of range";
+    // NaN or infinite geometry has no place in a tree (the device flatten checks the same, flatten.hip)
+    auto finite = [](const float* p, size_t n) {
+        float acc = 0.0f;
+        for (size_t i = 0; i < n; ++i) acc += p[i] - p[i];  // x - x: 0 for finite x, NaN otherwise
+        return acc == 0.0f;
+    };
+    if (!finite(s->tri_v, 9 * (size_t)s->n_tris)) return "tri_v holds a NaN or an infinity";
+    if (!finite(s->cone_base_r0, 4 * (size_t)s->n_cones)) return "cone_base_r0 holds a NaN or an infinity";
+    if (!finite(s->cone_apex_r1, 4 * (size_t)s->n_cones)) return "cone_apex_r1 holds a NaN or an infinity";
     if (hs.textured) {
         hs.tri_uv.assign(6 * (size_t)s->n_tris, 0.0f);
         hs.cone_h.assign(s->n_cones, 0.0f);
@@ -208,6 +218,8 @@ std::string flatten_scene(const khp_scene* s, HostScene& hs, bool objects) {
     for (unsigned t = 1; t < nt; ++t) th.emplace_back(work, t);
     work(0);
     for (auto& t : th) t.join();
+    if (!finite(hs.bounds.data(), hs.bounds.size()) || !finite(hs.centroid.data(), hs.centroid.size()))
+        return "an object's bounds or centroid overflow float32";
     hs.mats.assign(s->materials, s->materials + s->n_materials);
     hs.lights.resize(s->n_lights);
     for (uint32_t i = 0; i < s->n_lights; ++i) light_init(hs.lights[i], s->lights[i]);
@@ -239,6 +251,10 @@ static inline bool worth(const Box& b) {
     v3 d = b.mx - b.mn;
     return d.x > 0.0f && d.y > 0.0f && d.z > 0.0f;
 }
+static inline bool split_defined(const Box& b) {  // split_rule.h
+    const float mn[3] = {b.mn.x, b.mn.y, b.mn.z}, mx[3] = {b.mx.x, b.mx.y, b.mx.z};
+    return khp::split_defined(mn, mx);
+}
 
 struct Builder {
     HostScene& hs;
@@ -247,7 +263,8 @@ struct Builder {
     float cget(uint32_t oid, int axis) const { return cen[3 * (size_t)oid + axis]; }
     v3 cvec(uint32_t oid) const { return ld3(&cen[3 * (size_t)oid]); }
 
-    void partition(uint32_t first, uint32_t second, uint32_t& lsec, uint32_t& rfirst, const Box& cb, Box& lcb,
+    // false: no plane has a cost below FLT_MAX, nothing is moved (split_rule.h)
+    bool partition(uint32_t first, uint32_t second, uint32_t& lsec, uint32_t& rfirst, const Box& cb, Box& lcb,
                    Box& rcb) const {
         float best = FLT_MAX;
         int best_axis = 0, best_plane = 0;
@@ -301,6 +318,7 @@ struct Builder {
                 }
             }
         }
+        if (!cost_defined(best)) return false;
         const float cbmin = cbmins[best_axis], k = ks[best_axis];
         int left = (int)first, right = (int)second;
         bool ls = false, rs = false;
@@ -330,6 +348,7 @@ struct Builder {
             if (b > best_plane) { lsec = (uint32_t)(left - 1); rfirst = (uint32_t)left; }
             else { lsec = (uint32_t)left; rfirst = (uint32_t)(left + 1); }
         }
+        return true;
     }
 
     // BVHNode::split; nodes appended to `out` in DFS preorder, child indices relative to `out`.
@@ -347,10 +366,10 @@ struct Builder {
         out[ni].mn = bv.mn;
         out[ni].mx = bv.mx;
         if (depth > maxdepth) maxdepth = depth;
-        if (second - first > 1u && worth(cb)) {
-            uint32_t lsec, rfirst;
-            Box lcb, rcb;
-            partition(first, second, lsec, rfirst, cb, lcb, rcb);
+        uint32_t lsec = 0, rfirst = 0;
+        Box lcb = box_empty(), rcb = box_empty();
+        if (second - first > 1u && worth(cb) && split_defined(cb) &&
+            partition(first, second, lsec, rfirst, cb, lcb, rcb)) {
             out[ni].count = 0;
             if (par > 0 && second - first > 32768u) {
                 std::vector<BuildNode> L, R;

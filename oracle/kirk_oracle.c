@@ -646,8 +646,21 @@ static int32_t new_node(struct ko_ctx* c) {
 
 static float cent(const struct ko_ctx* c, uint32_t id, int axis) { return comp(c->obj[id].centroid, axis); }
 
-/* BVHNode::partition, binned SAH (CPU_BVH.cpp:357-552) */
-static void partition(struct ko_ctx* c, uint32_t first, uint32_t second, uint32_t* lr_second, uint32_t* rr_first,
+/* Where KIRK's recursion is undefined the node is a leaf (the product's
+ * split_rule.h): the centroid extent or k = 14.4f / extent of an axis is not finite (KIRK
+ * would index its 16 bins with a NaN or an out-of-range float converted to int), or no
+ * plane has a cost below FLT_MAX (KIRK would partition by uninitialised boxes). */
+static int split_defined(const box_t* b) {
+    for (int axis = 0; axis < 3; ++axis) {
+        const float cbdiff = comp(b->mx, axis) - comp(b->mn, axis);
+        const float k = (16.0f * (1.0f - 0.1f)) / cbdiff;
+        if (!isfinite(cbdiff) || !isfinite(k)) return 0;
+    }
+    return 1;
+}
+
+/* BVHNode::partition, binned SAH (CPU_BVH.cpp:357-552); 0 when no plane has a cost below FLT_MAX */
+static int partition(struct ko_ctx* c, uint32_t first, uint32_t second, uint32_t* lr_second, uint32_t* rr_first,
                       const box_t* centbox, box_t* lcb, box_t* rcb) {
     uint32_t* ids = c->ids;
     float best = FLT_MAX;
@@ -696,6 +709,7 @@ static void partition(struct ko_ctx* c, uint32_t first, uint32_t second, uint32_
             }
         }
     }
+    if (!(best < FLT_MAX)) return 0;
     const float cbmin = ac[best_axis].cbmin, k = ac[best_axis].k;
     int left = (int)first, right = (int)second;
     int ls = 0, rs = 0;
@@ -721,6 +735,7 @@ static void partition(struct ko_ctx* c, uint32_t first, uint32_t second, uint32_
         if (b > best_plane) { *lr_second = (uint32_t)(left - 1); *rr_first = (uint32_t)left; }
         else { *lr_second = (uint32_t)left; *rr_first = (uint32_t)(left + 1); }
     }
+    return 1;
 }
 
 /* BVHNode::split (CPU_BVH.cpp:95-138), leaf_threshold 1, unbounded depth (CPU_BVH.h:64) */
@@ -734,10 +749,10 @@ static int32_t split(struct ko_ctx* c, uint32_t first, uint32_t second, const bo
     }
     c->nodes[ni].box = bv;
     if (depth > c->depth) c->depth = depth;
-    if (second - first > 1u && box_worth(centbox)) {
-        uint32_t ls, rf;
-        box_t lcb, rcb;
-        partition(c, first, second, &ls, &rf, centbox, &lcb, &rcb);
+    uint32_t ls = 0, rf = 0;
+    box_t lcb = box_empty(), rcb = box_empty();
+    if (second - first > 1u && box_worth(centbox) && split_defined(centbox) &&
+        partition(c, first, second, &ls, &rf, centbox, &lcb, &rcb)) {
         int32_t l = split(c, first, ls, &lcb, depth + 1);
         int32_t r = split(c, rf, second, &rcb, depth + 1);
         c->nodes[ni].left = l; c->nodes[ni].right = r; c->nodes[ni].count = 0;
