@@ -21,12 +21,12 @@ def set_hw_queues(n: int = 8) -> None:
 
 from . import native  # noqa: E402,F401
 from .native import (AOV_CHANNELS, DENOISE_DEMODULATE, DENOISE_DEVICE, HAIR_LOBE_R, HAIR_LOBE_TRT,  # noqa: E402
-                     HAIR_LOBE_TT, MOMENTS_DEVICE, MOMENTS_PLANES, NOISE_CONTEXT, NOISE_MOMENTS, NOISE_PLANE,
-                     REPROJECT_DEVICE, REPROJECT_MATCH_OBJECT, AdaptiveParams, AovBuffers, DenoiseNoise, DenoiseParams,
-                     ReprojectFrame, ReprojectOut, ReprojectParams)
+                     HAIR_LOBE_TT, LENS_FOCUS_KIRK, LENS_FOCUS_PLANE, MOMENTS_DEVICE, MOMENTS_PLANES, NOISE_CONTEXT,
+                     NOISE_MOMENTS, NOISE_PLANE, REPROJECT_DEVICE, REPROJECT_MATCH_OBJECT, AdaptiveParams, AovBuffers,
+                     DenoiseNoise, DenoiseParams, ReprojectFrame, ReprojectOut, ReprojectParams)
 from .pathtracer import (BVH, BsdfFactory, HipContext, PathTracer, ShaderFactory, TemporalAccumulator,  # noqa: E402
-                         adaptive_select_host, comm_unique_id, denoise_host, denoise_var_host, moments_fold_host,
-                         moments_variance, reproject_host)
+                         adaptive_select_host, camera_rays_host, comm_unique_id, denoise_host, denoise_var_host,
+                         lens_from_kirk, moments_fold_host, moments_variance, reproject_host)
 from .scenes import SceneData, build_config  # noqa: E402
 
 __all__ = ["set_hw_queues", "native", "BVH", "BsdfFactory", "HipContext", "PathTracer", "ShaderFactory", "SceneData",
@@ -34,4 +34,5 @@ __all__ = ["set_hw_queues", "native", "BVH", "BsdfFactory", "HipContext", "PathT
            "AOV_CHANNELS", "DenoiseParams", "DENOISE_DEVICE", "DENOISE_DEMODULATE", "denoise_host", "MOMENTS_DEVICE",
            "MOMENTS_PLANES", "moments_fold_host", "moments_variance", "AdaptiveParams", "adaptive_select_host", "DenoiseNoise",
            "NOISE_PLANE", "NOISE_MOMENTS", "NOISE_CONTEXT", "denoise_var_host", "ReprojectParams", "ReprojectFrame",
-           "ReprojectOut", "REPROJECT_DEVICE", "REPROJECT_MATCH_OBJECT", "reproject_host", "TemporalAccumulator"]
+           "ReprojectOut", "REPROJECT_DEVICE", "REPROJECT_MATCH_OBJECT", "reproject_host", "TemporalAccumulator",
+           "LENS_FOCUS_KIRK", "LENS_FOCUS_PLANE", "lens_from_kirk", "camera_rays_host"]

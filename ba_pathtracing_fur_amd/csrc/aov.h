@@ -102,7 +102,8 @@ __device__ __forceinline__ void aov_record(const DevScene& S, const Wave& Wv, co
 
 // k_extend<false, true>'s loop over the chunk's paths (queue slot = path, one
 // fused frame), ending each path in aov_record instead of the hit columns.
-template <bool TEX>
+// LENS: the camera rays are lens rays (khp_set_lens, camera_path<true>).
+template <bool TEX, bool LENS = false>
 __global__ __launch_bounds__(TRAV_BLOCK, AOV_WAVES) void k_aov_trace(DevScene S, Wave Wv, SpillArea spill, AovCols R) {
     extern __shared__ uint32_t lds[];
     const uint32_t n = Wv.cnt->nq[0];
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(TRAV_BLOCK, AOV_WAVES) void k_aov_trace(DevScene S,
             const bool got = cl.claim(idle, my, exhausted);
             if (!has && got && cl.phys(my, idx)) {
                 uint32_t key_unused;
-                const Ray r = camera_path(S, Wv, idx, key_unused);
+                const Ray r = camera_path<LENS>(S, Wv, idx, key_unused);
                 trav_setup(tr, r);
                 h.t = FLT_MAX_;
                 h.slot = -1;
@@ -285,6 +286,7 @@ extern "C" khp_status khp_render_aov(khp_ctx* c, const khp_render_params* p, con
     Wv.pix_major = 1;
     Wv.fsample0[0] = p->first_sample;
     const SpillArea sp{A.spill.as<int4>(), (uint32_t)grid * TRAV_BLOCK};
+    const bool lens = c->S.lens.radius > 0.0f;   // khp_set_lens: the lens twins (the same launch bounds and grid)
     for (uint32_t p_off = 0; p_off < P_all; p_off += P_chunk) {
         const uint32_t P = std::min(P_chunk, P_all - p_off), n = P * spp;
         Wv.P = P;
@@ -292,7 +294,9 @@ extern "C" khp_status khp_render_aov(khp_ctx* c, const khp_render_params* p, con
         Wv.cap = n;
         HIPCHK(hipMemsetAsync(A.cnt.p, 0, sizeof(Counters), c->stream));
         hipLaunchKernelGGL(k_start, dim3(1), dim3(1), 0, c->stream, Wv.cnt, n);
-        if (tex) hipLaunchKernelGGL(k_aov_trace<true>, dim3(grid), dim3(TRAV_BLOCK), AOV_LDS_BYTES, c->stream, c->S, Wv, sp, R);
+        if (lens && tex) hipLaunchKernelGGL((k_aov_trace<true, true>), dim3(grid), dim3(TRAV_BLOCK), AOV_LDS_BYTES, c->stream, c->S, Wv, sp, R);
+        else if (lens) hipLaunchKernelGGL((k_aov_trace<false, true>), dim3(grid), dim3(TRAV_BLOCK), AOV_LDS_BYTES, c->stream, c->S, Wv, sp, R);
+        else if (tex) hipLaunchKernelGGL(k_aov_trace<true>, dim3(grid), dim3(TRAV_BLOCK), AOV_LDS_BYTES, c->stream, c->S, Wv, sp, R);
         else hipLaunchKernelGGL(k_aov_trace<false>, dim3(grid), dim3(TRAV_BLOCK), AOV_LDS_BYTES, c->stream, c->S, Wv, sp, R);
         hipLaunchKernelGGL(k_aov_reduce, dim3((P + 255) / 256), dim3(256), 0, c->stream, R, O, Wv.pix, p_off, P, spp);
         HIPCHK(hipGetLastError());

@@ -689,6 +689,58 @@ __global__ __launch_bounds__(DBG_BLOCK) void k_dbg_material(DevScene S, uint32_t
     }
 }
 
+// khp_debug_camera_rays: camera_path itself, over a chunk description of the items -- item
+// i is "pixel" i of an n-pixel list with one sample per pixel, and its sample index goes
+// in as the render-ahead offset, so the key is path_key(seed, pixels[i], samples[i]).  LENS
+// as the render kernels have it: the instance is chosen by the lens's radius.
+template <bool LENS>
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_camera_rays(DevScene S, Wave Wv, uint32_t n, const uint32_t* samples,
+                                                               float* orig, float* dir) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        uint32_t key_unused;
+        const Ray r = camera_path<LENS>(S, Wv, i, key_unused, samples[i]);
+        st3(orig + 3 * (size_t)i, r.o);
+        st3(dir + 3 * (size_t)i, r.d);
+    }
+}
+
+extern "C" khp_status khp_debug_camera_rays(khp_ctx* c, uint32_t width, uint32_t seed, uint32_t n,
+                                            const uint32_t* pixels, const uint32_t* samples, float* orig, float* dir) {
+    if (const char* why = camera_rays_error(nullptr, width, n, pixels, samples, orig, dir))
+        return fail(KHP_EINVAL, std::string("khp_debug_camera_rays: ") + why);
+    if (!c) return fail(KHP_EINVAL, "khp_debug_camera_rays: ctx is null");
+    if (!c->scene_set) return fail(KHP_ENOTREADY, "khp_debug_camera_rays: khp_set_scene first");
+    KHPCHK(drain(c));  // complete asynchronous frames first
+    HIPCHK(hipSetDevice(c->device));
+    DevMem px, sm, oo, od;
+    HIPCHK(upload(px, pixels, (size_t)n, c->stream));
+    HIPCHK(upload(sm, samples, (size_t)n, c->stream));
+    HIPCHK(oo.ensure(12 * (size_t)n));
+    HIPCHK(od.ensure(12 * (size_t)n));
+    DevScene S{};   // the kernel reads the camera and the lens only
+    S.cam = c->hs.cam;
+    S.lens = c->S.lens;
+    Wave Wv{};
+    Wv.pix = px.as<uint32_t>();
+    Wv.P = n;
+    Wv.W = width;
+    Wv.H = 1u;
+    Wv.seed = seed;
+    Wv.n_samples = 1u;
+    Wv.n_frames = 1u;
+    if (S.lens.radius > 0.0f)
+        hipLaunchKernelGGL(k_dbg_camera_rays<true>, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, S, Wv, n,
+                           sm.as<uint32_t>(), oo.as<float>(), od.as<float>());
+    else
+        hipLaunchKernelGGL(k_dbg_camera_rays<false>, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, S, Wv, n,
+                           sm.as<uint32_t>(), oo.as<float>(), od.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(orig, oo.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(dir, od.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the camera ray queries"));
+    return KHP_OK;
+}
+
 static khp_status dbg_textured(khp_ctx* c, const char* who) {
     if (!c->S.textured)
         return fail(KHP_EINVAL, std::string(who) + ": the scene has no textured material or environment map "

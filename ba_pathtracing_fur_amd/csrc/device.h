@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kmath.h"
+#include "lens.h"
 #include "scene.h"
 
 namespace khp {
@@ -47,6 +48,7 @@ struct DevScene {
     const float4* __restrict__ top;
     int32_t top_root;
     uint32_t hair_lobes;   // khp_set_hair_lobes: KHP_HAIR_LOBE_* bits, read by KINDS_LOBES instances only
+    khp_lens lens;         // khp_set_lens: radius 0 (the default) is the pinhole camera (lens.h)
 };
 
 // ---- textures (ABI 6) -------------------------------------------------------------------

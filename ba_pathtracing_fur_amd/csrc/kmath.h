@@ -336,7 +336,8 @@ KHD float draw_u01(uint32_t key, uint32_t dim) { return (float)(draw_u32(key, di
 enum Purpose : uint32_t {
     P_CAM_X = 0, P_CAM_Y = 1, P_BSDF_0 = 2, P_BSDF_1 = 3, P_LIGHT_SEL = 4, P_LIGHT_0 = 5, P_LIGHT_1 = 6,
     P_HAIR_ALPHA = 7, P_HAIR_BETA = 8,
-    P_HAIR_LOBE = 9   // khp_set_hair_lobes: the lobe of an unflagged first hit (hair_lobes.h)
+    P_HAIR_LOBE = 9,  // khp_set_hair_lobes: the lobe of an unflagged first hit (hair_lobes.h)
+    P_LENS_U = 10, P_LENS_V = 11   // khp_set_lens: the lens point of a camera ray, bounce 0 only (lens.h)
 };
 KHD uint32_t dim_of(uint32_t bounce, uint32_t purpose) { return bounce * 16u + purpose; }
 

@@ -198,6 +198,11 @@ __device__ __forceinline__ T wave_sum(T v) {
 // Camera ray and RNG key of path pid.  k_generate writes them to the bounce-0
 // queue; with Wave::cam0 set, k_extend and k_shade compute them in place at
 // bounce 0 instead (queue slot = path there), the same operations.
+// LENS: the instances behind khp_set_lens (S.lens.radius > 0; the plan picks them, as it picks
+// the lobe instances), which turn the pinhole ray into the thin-lens ray of lens.h.  Instances
+// of their own, because a branch on the radius cost the default traversal kernels scratch
+// (DESIGN.md §21); without LENS the operations are the pinhole ray's alone.
+template <bool LENS = false>
 __device__ __forceinline__ Ray camera_path(const DevScene& S, const Wave& Wv, uint32_t pid, uint32_t& key,
                                            uint32_t s_off = 0u) {
     // the samples of one pixel are adjacent paths (path_coords), so a wave traces
@@ -208,13 +213,13 @@ __device__ __forceinline__ Ray camera_path(const DevScene& S, const Wave& Wv, ui
     const uint32_t pixel = Wv.pix[Wv.p_off + p_local];
     const uint32_t x = pixel % Wv.W, y = pixel / Wv.W;
     key = path_key(Wv.seed, pixel, Wv.fsample0[fr] + s_local + s_off);
-    const float u1 = draw_u01(key, dim_of(0, P_CAM_X)), u2 = draw_u01(key, dim_of(0, P_CAM_Y));
-    const khp_camera& cam = S.cam;
-    const float s1 = ((float)x + u1) * cam.pixel_size, s2 = ((float)y + u2) * cam.pixel_size;
-    const v3 dir = ((ld3(cam.bottom_left) + ld3(cam.axis_x) * s1) + ld3(cam.axis_y) * s2) - ld3(cam.position);
-    return make_ray(ld3(cam.position), dir);
+    Ray r;
+    pinhole_ray(S.cam, x, y, key, r.o, r.d);
+    if constexpr (LENS) lens_ray(S.cam, S.lens, key, r.o, r.d, r.o, r.d);
+    return r;
 }
 
+template <bool LENS = false>
 __global__ __launch_bounds__(256) void k_generate(DevScene S, Wave Wv) {
     uint32_t n = Wv.P * Wv.n_samples * Wv.n_frames;
     uint32_t pid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -224,7 +229,7 @@ __global__ __launch_bounds__(256) void k_generate(DevScene S, Wave Wv) {
     }
     if (pid >= n) return;
     uint32_t key;
-    const Ray r = camera_path(S, Wv, pid, key);
+    const Ray r = camera_path<LENS>(S, Wv, pid, key);
     Wv.qo[0][0][pid] = r.o.x; Wv.qo[0][1][pid] = r.o.y; Wv.qo[0][2][pid] = r.o.z;
     Wv.qd[0][0][pid] = r.d.x; Wv.qd[0][1][pid] = r.d.y; Wv.qd[0][2][pid] = r.d.z;
     Wv.qpid[0][pid] = pid;
@@ -500,7 +505,8 @@ __global__ __launch_bounds__(256) void k_pix_order(const uint32_t* __restrict__ 
 // the camera ray, computed here instead of loaded.
 // WIDE: the two-level records (S.wide, traverse.h iterw) instead of the 64-B loop.
 // TOP: the tree's top records staged in LDS (khp_ctx_params.lds_nodes; 64-B loop only).
-template <bool STATS, bool CAM = false, bool WIDE = false, bool TOP = false>
+// LENS (CAM instances only): the camera rays are lens rays (khp_set_lens, camera_path<true>).
+template <bool STATS, bool CAM = false, bool WIDE = false, bool TOP = false, bool LENS = false>
 __global__ __launch_bounds__(TRAV_BLOCK, WIDE ? EXT_WAVES_W : CAM ? CAM_WAVES : EXT_WAVES) void k_extend(DevScene S, Wave Wv, int cur, SpillArea spill) {
     extern __shared__ uint32_t lds[];
     const uint32_t nf = Wv.cnt->nq[cur], nb = Wv.cnt->nqb[cur];
@@ -546,7 +552,7 @@ __global__ __launch_bounds__(TRAV_BLOCK, WIDE ? EXT_WAVES_W : CAM ? CAM_WAVES : 
                 Ray r;
                 if (CAM) {
                     uint32_t key_unused;
-                    r = camera_path(S, Wv, idx, key_unused);
+                    r = camera_path<LENS>(S, Wv, idx, key_unused);
                 } else {
                     r.o = mk(Wv.qo[cur][0][idx], Wv.qo[cur][1][idx], Wv.qo[cur][2][idx]);
                     r.d = mk(Wv.qd[cur][0][idx], Wv.qd[cur][1][idx], Wv.qd[cur][2][idx]);
@@ -587,16 +593,22 @@ __global__ __launch_bounds__(TRAV_BLOCK, WIDE ? EXT_WAVES_W : CAM ? CAM_WAVES : 
 }
 
 // Host-side launch of the k_extend instance for (stats, camera rays in place, wide records).
+// The camera-bounce instances have a lens twin each (khp_set_lens: S.lens.radius > 0).
 static void launch_extend(bool stats, bool cam, bool wide, int grid, hipStream_t s, const DevScene& S, const Wave& W,
                           int cur, SpillArea sp, bool top = false) {
     const dim3 g(grid), b(TRAV_BLOCK);
+    const bool lens = cam && S.lens.radius > 0.0f;
     if (top && !stats && !wide && S.top) {   // the top records in LDS (lds_nodes)
-        if (cam) hipLaunchKernelGGL((k_extend<false, true, false, true>), g, b, CAM_LDS_BYTES + TOP_LDS_BYTES, s, S, W, cur, sp);
+        if (lens) hipLaunchKernelGGL((k_extend<false, true, false, true, true>), g, b, CAM_LDS_BYTES + TOP_LDS_BYTES, s, S, W, cur, sp);
+        else if (cam) hipLaunchKernelGGL((k_extend<false, true, false, true>), g, b, CAM_LDS_BYTES + TOP_LDS_BYTES, s, S, W, cur, sp);
         else hipLaunchKernelGGL((k_extend<false, false, false, true>), g, b, EXT_LDS_BYTES + TOP_LDS_BYTES, s, S, W, cur, sp);
         return;
     }
-#define KHP_EXT(ST, CA, WI) \
-    hipLaunchKernelGGL((k_extend<ST, CA, WI>), g, b, CA ? CAM_LDS_BYTES : EXT_LDS_BYTES, s, S, W, cur, sp)
+#define KHP_EXT(ST, CA, WI)                                                                                        \
+    do {                                                                                                           \
+        if (CA && lens) hipLaunchKernelGGL((k_extend<ST, CA, WI, false, CA>), g, b, CAM_LDS_BYTES, s, S, W, cur, sp); \
+        else hipLaunchKernelGGL((k_extend<ST, CA, WI>), g, b, CA ? CAM_LDS_BYTES : EXT_LDS_BYTES, s, S, W, cur, sp); \
+    } while (0)
     if (wide) {
         if (stats) { if (cam) KHP_EXT(true, true, true); else KHP_EXT(true, false, true); }
         else { if (cam) KHP_EXT(false, true, true); else KHP_EXT(false, false, true); }
@@ -1286,7 +1298,8 @@ __device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, floa
 #ifndef KHP_SHADE_WAVES
 #define KHP_SHADE_WAVES 1   // min waves per SIMD for k_shade's register budget (1: unconstrained)
 #endif
-template <bool TEX, bool BD, uint32_t KINDS = 0xFFFFFFFFu>
+// LENS: bounce 0's recomputed camera rays are lens rays (khp_set_lens; launched for that bounce only).
+template <bool TEX, bool BD, uint32_t KINDS = 0xFFFFFFFFu, bool LENS = false>
 __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_shade(DevScene S, Wave Wv, int cur, uint32_t bounce) {
     const uint32_t nf = Wv.cnt->nq[cur], n = nf + Wv.cnt->nqb[cur];
     const int nxt = cur ^ 1;
@@ -1309,7 +1322,7 @@ __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_s
             if (bounce == 0 && Wv.cam0) {  // the bounce-0 state k_generate would have queued
                 uint32_t key0;
                 pid = i;
-                r = camera_path(S, Wv, i, key0);
+                r = camera_path<LENS>(S, Wv, i, key0);
                 tf = make_float4(1.0f, 1.0f, 1.0f, f_from_bits(0u));
                 ck = make_float4(0.0f, 0.0f, 0.0f, f_from_bits(key0));
             } else {
@@ -1430,8 +1443,16 @@ constexpr uint32_t KINDS_FUR = (1u << KHP_BSDF_LAMBERTIAN_REFLECTION) | (1u << K
 static void launch_shade(bool tex, bool bd, bool fur, bool lobes, int grid, int grid_bd, hipStream_t s,
                          const DevScene& S, const Wave& W, int cur, uint32_t bounce) {
     constexpr uint32_t DEFAULTED = 0xFFFFFFFFu;
-#define KHP_SHADE(TEX, BD, K) \
-    hipLaunchKernelGGL((k_shade<TEX, BD, K>), dim3(BD ? grid_bd : grid), dim3(shade_block<TEX, BD>()), 0, s, S, W, cur, bounce)
+    // khp_set_lens: the lens twin, for the one launch that recomputes camera rays (never with the light-path variant)
+    const bool lens = !bd && bounce == 0u && W.cam0 != 0u && S.lens.radius > 0.0f;
+#define KHP_SHADE(TEX, BD, K)                                                                                          \
+    do {                                                                                                               \
+        if (!BD && lens)                                                                                               \
+            hipLaunchKernelGGL((k_shade<TEX, BD, K, !BD>), dim3(grid), dim3(shade_block<TEX, BD>()), 0, s, S, W, cur, bounce); \
+        else                                                                                                           \
+            hipLaunchKernelGGL((k_shade<TEX, BD, K>), dim3(BD ? grid_bd : grid), dim3(shade_block<TEX, BD>()), 0, s, S, W, \
+                               cur, bounce);                                                                           \
+    } while (0)
     if (lobes && tex) KHP_SHADE(true, false, KINDS_ALL | KINDS_LOBES);   // TT / TRT compiled in
     else if (lobes && fur) KHP_SHADE(false, false, KINDS_FUR | KINDS_LOBES);
     else if (lobes) KHP_SHADE(false, false, KINDS_ALL | KINDS_LOBES);
@@ -1793,7 +1814,8 @@ __device__ unsigned long long g_ra_prof[2];
 // path state (TFq / CKq, moved as k_shade and the shadow finish left them) -- and
 // carries them through the remaining bounces; paths of a chunk that ended earlier
 // already wrote their colour.
-template <bool TEX, bool WIDE, uint32_t KINDS, bool RA, bool QS = false>
+// LENS (never with QS, whose launches make no camera ray): the camera rays are lens rays (khp_set_lens).
+template <bool TEX, bool WIDE, uint32_t KINDS, bool RA, bool QS = false, bool LENS = false>
 __global__ __launch_bounds__(TRAV_BLOCK, PATH_WAVES) void k_path(DevScene S, Wave Wv, SpillArea spill, PathLanes L, Ahead A) {
     extern __shared__ uint32_t lds[];
     const uint32_t npaths = Wv.P * Wv.n_samples * Wv.n_frames;
@@ -1998,7 +2020,7 @@ __global__ __launch_bounds__(TRAV_BLOCK, PATH_WAVES) void k_path(DevScene S, Wav
                 }
                 if (cam) {
                     uint32_t key;
-                    sray = camera_path(S, Wv, cpid & PID_MASK, key, coff);
+                    sray = camera_path<LENS>(S, Wv, cpid & PID_MASK, key, coff);
                     L.col[0][g] = make_float4(1.0f, 1.0f, 1.0f, f_from_bits(0u));
                     L.col[1][g] = make_float4(0.0f, 0.0f, 0.0f, f_from_bits(key));
                     L.col[2][g] = make_float4(0.0f, 0.0f, 0.0f, f_from_bits(cpid));
@@ -2140,6 +2162,11 @@ static void launch_path_k(int grid, hipStream_t s, const DevScene& S, const Wave
                           const Ahead& A, bool qs) {
     if (qs) {
         hipLaunchKernelGGL((k_path<TEX, WIDE, K, false, true>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
+        return;
+    }
+    if (S.lens.radius > 0.0f) {   // khp_set_lens: the lens twins
+        if (A.on) hipLaunchKernelGGL((k_path<TEX, WIDE, K, true, false, true>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
+        else hipLaunchKernelGGL((k_path<TEX, WIDE, K, false, false, true>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
         return;
     }
     if (A.on) hipLaunchKernelGGL((k_path<TEX, WIDE, K, true>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
@@ -2676,7 +2703,8 @@ struct khp_ctx {
     int grid_sh_w = 0;     // k_shadow on the two-level records
     int grid_path = 0, grid_path_w = 0;   // k_path (64-B / two-level records)
     uint32_t bsdf_kinds = 0;              // the BSDF kinds the scene's materials use (bit per khp_bsdf_kind)
-    // (khp_set_hair_lobes keeps its mask in S.hair_lobes: the scene build leaves it alone)
+    // (khp_set_hair_lobes keeps its mask in S.hair_lobes, khp_set_lens its lens in S.lens: the
+    // scene build leaves both alone)
     int grid_ext_max = 0;  // the k_extend spill columns are sized for the largest grid
     khp_stats st{};
     // rccl gather: pixel lists cached per (W, H, tile, nranks, rank, root)
@@ -3019,6 +3047,8 @@ extern "C" khp_status khp_set_bdpt(khp_ctx* c, const khp_bdpt_params* p) {
     if (!c || !p) return fail(KHP_EINVAL, "null argument");
     if (p->enabled && c->S.hair_lobes != HAIR_LOBE_R)
         return fail(KHP_EUNSUPPORTED, "the light-path variant traces the R lobe only: khp_set_hair_lobes(R) first");
+    if (p->enabled && c->S.lens.radius > 0.0f)
+        return fail(KHP_EUNSUPPORTED, "the light-path variant's image-plane stage assumes a pinhole sensor: khp_set_lens(radius 0) first");
     if (p->enabled && (p->light_paths < 1 || p->light_paths > 65536))
         return fail(KHP_EINVAL, "light_paths must be 1..65536");
     if (p->enabled && (p->vertices < 1 || p->vertices > 16)) return fail(KHP_EINVAL, "vertices must be 1..16");
@@ -3057,6 +3087,26 @@ extern "C" khp_status khp_set_hair_lobes(khp_ctx* c, const khp_hair_lobes* p) {
     return KHP_OK;
 }
 
+extern "C" khp_status khp_get_lens(khp_ctx* c, khp_lens* out) {
+    if (!c || !out) return fail(KHP_EINVAL, "khp_get_lens: null argument");
+    *out = c->S.lens;
+    return KHP_OK;
+}
+
+// The thin-lens camera (lens.h).  Nothing is rebuilt: camera_path reads S.lens.
+extern "C" khp_status khp_set_lens(khp_ctx* c, const khp_lens* p) {
+    if (const char* why = lens_error(p)) return fail(KHP_EINVAL, std::string("khp_set_lens: ") + why);
+    if (!c) return fail(KHP_EINVAL, "khp_set_lens: ctx is null");
+    if (p->radius > 0.0f && c->bd.enabled)
+        return fail(KHP_EUNSUPPORTED, "khp_set_lens: the light-path variant's image-plane stage assumes a pinhole sensor: disable khp_set_bdpt first");
+    HIPCHK(hipSetDevice(c->device));
+    khp_status dr = drain(c);  // frames in flight finish with the lens they started with
+    if (dr != KHP_OK) return dr;
+    c->S.lens = *p;
+    ++c->gen;
+    return KHP_OK;
+}
+
 extern "C" khp_status khp_set_camera(khp_ctx* c, const khp_camera* cam) {
     if (!c || !cam) return fail(KHP_EINVAL, "null argument");
     HIPCHK(hipSetDevice(c->device));
@@ -3081,6 +3131,7 @@ extern "C" khp_status khp_create(khp_ctx** out, int device, uint32_t flags) {
     khp_ctx_params_defaults(&c->prm);
     khp_bdpt_params_defaults(&c->bd);
     c->S.hair_lobes = HAIR_LOBE_R;
+    khp_lens_defaults(&c->S.lens);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -4299,7 +4350,9 @@ static khp_status enqueue_chunk(khp_ctx* c, const BatchPlan& pl, const khp_rende
     }
     timed(c, f, T_OTHER, true, sA);
     if (!pl.use_path && Wv.cam0) hipLaunchKernelGGL(k_start, dim3(1), dim3(1), 0, sA, Wv.cnt, npaths);
-    else if (!pl.use_path) hipLaunchKernelGGL(k_generate, dim3((npaths + 255) / 256), dim3(256), 0, sA, c->S, Wv);
+    else if (!pl.use_path && c->S.lens.radius > 0.0f)   // khp_set_lens: the lens twin
+        hipLaunchKernelGGL(k_generate<true>, dim3((npaths + 255) / 256), dim3(256), 0, sA, c->S, Wv);
+    else if (!pl.use_path) hipLaunchKernelGGL(k_generate<false>, dim3((npaths + 255) / 256), dim3(256), 0, sA, c->S, Wv);
     if (pl.bdm) {  // the light subpaths of this chunk's sample slots (frames x samples)
         const uint32_t nsub = pl.nf * ns * c->bd.light_paths * (uint32_t)c->S.n_lights;
         hipLaunchKernelGGL(k_light_paths, dim3((nsub + 63) / 64), dim3(64), 0, sA, c->S, Wv);

@@ -149,6 +149,17 @@ class HairLobes(ctypes.Structure):
     _fields_ = [("lobes", c_uint32), ("reserved", c_uint32)]
 
 
+LENS_FOCUS_KIRK, LENS_FOCUS_PLANE = 0, 1
+
+
+class Lens(ctypes.Structure):
+    """khp_lens (16 bytes): the thin-lens camera; radius 0 is the pinhole."""
+    _fields_ = [("radius", c_float), ("focus_distance", c_float), ("focus", c_uint32), ("reserved", c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {"radius": float(self.radius), "focus_distance": float(self.focus_distance), "focus": int(self.focus)}
+
+
 class AovBuffers(ctypes.Structure):
     """khp_aov_buffers (48 bytes): the planes khp_render_aov writes; a null plane is not computed."""
     _fields_ = [("normal", POINTER(c_float)), ("albedo", POINTER(c_float)), ("tangent", POINTER(c_float)),
@@ -345,7 +356,8 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_adaptive_select_host", "khp_debug_adaptive_select", "khp_debug_adaptive_list",
             "khp_denoise_noise_defaults", "khp_denoise_var", "khp_denoise_var_host",
             "khp_reproject_params_defaults", "khp_reproject", "khp_reproject_host", "khp_debug_tex_color",
-            "khp_debug_env_color", "khp_debug_material"]
+            "khp_debug_env_color", "khp_debug_material", "khp_lens_defaults", "khp_lens_from_kirk", "khp_set_lens",
+            "khp_get_lens", "khp_camera_rays_host", "khp_debug_camera_rays"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
 ABI_VERSION = 17
@@ -470,6 +482,14 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_hair_lobes_defaults": (None, [P(HairLobes)]),
         "khp_set_hair_lobes": (c_int, [c_void_p, P(HairLobes)]),
         "khp_get_hair_lobes": (c_int, [c_void_p, P(HairLobes)]),
+        "khp_lens_defaults": (None, [P(Lens)]),
+        "khp_lens_from_kirk": (c_int, [c_float, c_float, c_float, P(Lens)]),
+        "khp_set_lens": (c_int, [c_void_p, P(Lens)]),
+        "khp_get_lens": (c_int, [c_void_p, P(Lens)]),
+        "khp_camera_rays_host": (c_int, [P(Camera), P(Lens), c_uint32, c_uint32, c_uint32, P(c_uint32), P(c_uint32),
+                                         P(c_float), P(c_float)]),
+        "khp_debug_camera_rays": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, P(c_uint32), P(c_uint32), P(c_float),
+                                          P(c_float)]),
         "khp_debug_hair_sample": (c_int, [c_void_p, c_uint32, c_uint32, P(c_int32), P(c_int32), P(c_float), P(c_float),
                                           P(c_float), P(c_float), P(c_int32), P(c_float), P(c_float), P(c_float),
                                           P(c_float), P(c_int32), P(c_int32)]),

@@ -232,6 +232,31 @@ class HipContext:
         N.check(self.lib, self.lib.khp_get_hair_lobes(self.ptr, ctypes.byref(prm)), "khp_get_hair_lobes")
         return int(prm.lobes)
 
+    def set_lens(self, radius: float, focus_distance: float = 11.0, focus: int = N.LENS_FOCUS_KIRK) -> dict:
+        """khp_set_lens: the thin-lens camera of the next renders (KIRK's Camera::transformToDof,
+        which its path tracer never calls).  radius 0, the default, is the pinhole; focus is
+        LENS_FOCUS_KIRK (in focus: a sphere about the camera) or LENS_FOCUS_PLANE (a plane at
+        right angles to the axis); nothing is rebuilt.  Returns the previous lens()."""
+        old = self.lens()
+        prm = N.Lens(float(radius), float(focus_distance), int(focus), 0)
+        N.check(self.lib, self.lib.khp_set_lens(self.ptr, ctypes.byref(prm)), "khp_set_lens")
+        return old
+
+    def lens(self) -> dict:
+        """khp_get_lens: radius, focus_distance and focus of the context's lens."""
+        prm = N.Lens()
+        N.check(self.lib, self.lib.khp_get_lens(self.ptr, ctypes.byref(prm)), "khp_get_lens")
+        return prm.as_dict()
+
+    def debug_camera_rays(self, width: int, pixels, samples, seed: int = 0x4B49524B):
+        """khp_debug_camera_rays: the renderer's own camera rays (origins, directions) of the
+        (pixel, sample) pairs, with the context's camera and lens; nothing of the context is touched."""
+        px, sm = _ray_items(pixels, samples)
+        o, d = np.empty((len(px), 3), np.float32), np.empty((len(px), 3), np.float32)
+        N.check(self.lib, self.lib.khp_debug_camera_rays(self.ptr, int(width), int(seed), len(px), N.uptr(px),
+                                                         N.uptr(sm), N.fptr(o), N.fptr(d)), "khp_debug_camera_rays")
+        return o, d
+
     def render(self, width, height, spp, depth, seed=0x4B49524B, first_sample=0, tile_size=64, tile_rank=0,
                tile_nranks=1, out: np.ndarray | None = None, readback=True, stats=False,
                async_: bool = False) -> np.ndarray | None:
@@ -787,6 +812,44 @@ class HipContext:
     def gather_framebuffer(self, width, height, spp, depth, tile_size, nranks, rank, root=0):
         p = N.RenderParams(width, height, spp, depth, 0, 0, tile_size, rank, nranks, 0)
         N.check(self.lib, self.lib.khp_gather_framebuffer(self.ptr, ctypes.byref(p), root), "khp_gather_framebuffer")
+
+
+def _ray_items(pixels, samples):
+    """The (pixel, sample) pairs of a camera-ray query as two uint32 arrays of one length."""
+    px = np.ascontiguousarray(pixels, np.uint32).reshape(-1)
+    sm = np.ascontiguousarray(samples, np.uint32).reshape(-1)
+    if len(sm) == 1 and len(px) > 1:
+        sm = np.full(len(px), sm[0], np.uint32)
+    if len(px) != len(sm):
+        raise ValueError("pixels and samples must have one length")
+    return px, sm
+
+
+def lens_from_kirk(focal_length: float, f_stop: float, focus_distance: float) -> dict:
+    """khp_lens_from_kirk: KIRK's Camera members as set_lens arguments: radius = (focal_length /
+    f_stop) * 3 (m_aperture, times the factor of transformToDof's diskRand), focus KIRK."""
+    lib = N.load_library()
+    prm = N.Lens()
+    N.check(lib, lib.khp_lens_from_kirk(float(focal_length), float(f_stop), float(focus_distance), ctypes.byref(prm)),
+            "khp_lens_from_kirk")
+    return prm.as_dict()
+
+
+def camera_rays_host(camera: "N.Camera", width: int, pixels, samples, lens: dict | None = None,
+                     seed: int = 0x4B49524B):
+    """khp_camera_rays_host: the camera rays (origins, directions) khp_render traces for the
+    (pixel, sample) pairs, as a plain host loop over the kernels' own function; lens: a dict of
+    radius, focus_distance and focus (lens() / lens_from_kirk()), None for the pinhole."""
+    lib = N.load_library()
+    px, sm = _ray_items(pixels, samples)
+    o, d = np.empty((len(px), 3), np.float32), np.empty((len(px), 3), np.float32)
+    prm = None
+    if lens is not None:
+        prm = ctypes.byref(N.Lens(float(lens["radius"]), float(lens.get("focus_distance", 11.0)),
+                                  int(lens.get("focus", N.LENS_FOCUS_KIRK)), 0))
+    N.check(lib, lib.khp_camera_rays_host(ctypes.byref(camera), prm, int(width), int(seed), len(px), N.uptr(px),
+                                          N.uptr(sm), N.fptr(o), N.fptr(d)), "khp_camera_rays_host")
+    return o, d
 
 
 def _frame_check(name, a, width, height):

@@ -837,6 +837,69 @@ void khp_hair_lobes_defaults(khp_hair_lobes* out);   /* lobes = KHP_HAIR_LOBE_R 
 khp_status khp_set_hair_lobes(khp_ctx* ctx, const khp_hair_lobes* lobes);
 khp_status khp_get_hair_lobes(khp_ctx* ctx, khp_hair_lobes* out);
 
+/* ---- a thin-lens camera: depth of field ---------------------------------------
+ * KIRK::Camera holds m_focus_distance (11) and m_f_stop (1.8), derives m_aperture =
+ * m_focal_length / m_f_stop and builds lens rays in Camera::transformToDof
+ * (Common/Camera.cpp:39-51); only its Whitted tracer calls that (Simple_CPU_Raytracer.cpp:
+ * 58-60, 238-249), the path tracer never does.  A context therefore starts with radius 0,
+ * and with radius 0 every frame, texture, AOV plane and query is what it was before: the
+ * camera ray is the pinhole ray and no new random number is drawn.  With radius > 0 every
+ * camera ray of khp_render, khp_render_adaptive and khp_render_aov, on every schedule, is
+ * the lens ray below, one float32 operation per step in the order written (csrc/lens.h,
+ * compiled for the host and for gfx950: the same bits):
+ *   (p, d)   the pinhole ray of the path: p = camera.position, d its normalised direction;
+ *   u, v     draws 10 and 11 of bounce 0 of the path's key (unused before);
+ *   disk     Shirley and Chiu's concentric map of (u, v): a = 2u - 1, b = 2v - 1; a == 0
+ *            and b == 0 give (0, 0); |a| > |b| gives r = a, phi = (pi/4)(b/a); otherwise
+ *            r = b, phi = pi/2 - (pi/4)(a/b); the point (r cos phi, r sin phi), times
+ *            radius: (lx, ly).  Uniform over the disk, the distribution of KIRK's
+ *            glm::diskRand(m_aperture * 3) (rejection from rand()), here a function of the key;
+ *   focus    ft = focus_distance (KHP_LENS_FOCUS_KIRK, Camera.cpp:41 as written: the point
+ *            lies at focus_distance along the pixel's own ray, so the surface in focus is a
+ *            sphere about the camera), or focus_distance / dot(d, fwd) with fwd =
+ *            normalize(cross(axis_y, axis_x)) (KHP_LENS_FOCUS_PLANE: a plane at right angles
+ *            to the axis; where dot(d, fwd) is not > 0, ft = focus_distance); f = p + d * ft;
+ *   ray      start = (p + axis_x * lx) + axis_y * ly (Camera.cpp:45), direction
+ *            normalize(f - start) (KIRK's glm::normalize(ndir) discards its result; the Ray
+ *            constructor normalises).
+ * khp_set_lens completes in-flight frames (they finish with the lens they started with),
+ * drops render-ahead work and needs no rebuild; the framebuffer and the moments are not
+ * touched; khp_set_scene and khp_set_camera leave the lens alone.  KHP_EINVAL (checked
+ * before the context is touched; khp_last_error names the cause): a null argument, radius
+ * negative or not finite, focus_distance not finite or <= 0, an unknown focus, reserved !=
+ * 0.  The light-path variant's image-plane stage assumes a pinhole sensor: radius > 0
+ * while it is enabled, and enabling it while radius > 0, is KHP_EUNSUPPORTED.  A refused
+ * call changes nothing.  Lens-on frames have no CPU oracle.
+ * khp_reproject keeps its pinhole model: under a lens a pixel's depth plane is measured
+ * from a point of the lens, not from camera.position, so its `locate` step is off by at
+ * most radius. */
+#define KHP_LENS_FOCUS_KIRK  0u
+#define KHP_LENS_FOCUS_PLANE 1u
+typedef struct {
+    float radius;           /* offset 0: lens radius in scene units; 0: a pinhole (the default) */
+    float focus_distance;   /* 4: finite, > 0 */
+    uint32_t focus;         /* 8: KHP_LENS_FOCUS_* */
+    uint32_t reserved;      /* 12: 0 */
+} khp_lens;                 /* 16 bytes */
+void       khp_lens_defaults(khp_lens* out);   /* 0 (off), 11 (Camera.h:116), KIRK, 0 */
+/* radius = (focal_length / f_stop) * 3.0f: m_aperture, times diskRand's factor; focus KIRK.
+ * KHP_EINVAL: out null; focal_length, f_stop or focus_distance not finite and > 0. */
+khp_status khp_lens_from_kirk(float focal_length, float f_stop, float focus_distance, khp_lens* out);
+khp_status khp_set_lens(khp_ctx* ctx, const khp_lens* lens);
+khp_status khp_get_lens(khp_ctx* ctx, khp_lens* out);
+/* The definition as a plain host loop (no device, no context): item i is the camera ray of
+ * sample samples[i] of pixel pixels[i] (y * width + x) under `seed`, as khp_render makes
+ * it; orig and dir take 3 floats per item.  lens NULL or radius 0: the pinhole rays.
+ * KHP_EINVAL: a null camera or array, width 0, n outside [1, 2^20], a lens khp_set_lens
+ * would refuse. */
+khp_status khp_camera_rays_host(const khp_camera* camera, const khp_lens* lens, uint32_t width, uint32_t seed,
+                                uint32_t n, const uint32_t* pixels, const uint32_t* samples, float* orig, float* dir);
+/* Test hook in the style of the khp_debug_* queries: one thread per item runs the
+ * renderer's own camera-ray function with the context's camera and lens, on scratch of
+ * its own; nothing of the context is touched.  Needs a scene; otherwise as above. */
+khp_status khp_debug_camera_rays(khp_ctx* ctx, uint32_t width, uint32_t seed, uint32_t n, const uint32_t* pixels,
+                                 const uint32_t* samples, float* orig, float* dir);
+
 /* Completes every frame enqueued with KHP_RENDER_ASYNC (ABI 5).  A progressive
  * caller (KIRK's PathTracer::render loop) enqueues its passes and syncs before
  * reading the texture; passes accumulate in call order.  Any synchronous call

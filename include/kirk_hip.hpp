@@ -191,6 +191,23 @@ class Context {
         const khp_hair_lobes p{lobes, 0u};
         check(khp_set_hair_lobes(c_, &p), "khp_set_hair_lobes");
     }
+    // The thin-lens camera (khp_set_lens): radius 0, the default, is KIRK's pinhole path tracer;
+    // khp_lens_from_kirk maps Camera's m_focal_length, m_f_stop and m_focus_distance onto it
+    khp_lens lens() {
+        khp_lens p{};
+        check(khp_get_lens(c_, &p), "khp_get_lens");
+        return p;
+    }
+    void set_lens(const khp_lens& p) { check(khp_set_lens(c_, &p), "khp_set_lens"); }
+    void set_lens(float radius, float focus_distance, uint32_t focus = KHP_LENS_FOCUS_KIRK) {
+        const khp_lens p{radius, focus_distance, focus, 0u};
+        set_lens(p);
+    }
+    // test hook: the renderer's own camera rays of n (pixel, sample) pairs, 3 floats per item each
+    void debug_camera_rays(uint32_t width, uint32_t seed, uint32_t n, const uint32_t* pixels, const uint32_t* samples,
+                           float* orig, float* dir) {
+        check(khp_debug_camera_rays(c_, width, seed, n, pixels, samples, orig, dir), "khp_debug_camera_rays");
+    }
     void render(const khp_render_params& p, float* out_rgb = nullptr) {
         check(khp_render(c_, &p, out_rgb), "khp_render");
     }
