@@ -141,6 +141,19 @@ __global__ __launch_bounds__(DBG_BLOCK) void k_dbg_bsdf_eval(DevScene S, uint32_
     }
 }
 
+// The same with BSDF kind 11 compiled in (hair_pb.h): launched when an item is of that kind.
+__global__ __launch_bounds__(DBG_BLOCK) void k_dbg_bsdf_eval_hair(DevScene S, uint32_t n, const uint32_t* slot,
+                                                                  const int32_t* mat, const float* in, const float* nrm,
+                                                                  const float* out, float* f) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        ShadeCtx s;
+        dbg_frame(S, slot[i], s);
+        s.m = &S.mats[mat[i]];
+        s.n = ld3(nrm + 3 * (size_t)i);
+        st3(f + 3 * (size_t)i, bsdf_eval<KINDS_ALL_HAIR>(s, ld3(in + 3 * (size_t)i), ld3(out + 3 * (size_t)i)));
+    }
+}
+
 __global__ __launch_bounds__(DBG_BLOCK) void k_dbg_light_dir(DevScene S, uint32_t n, const int32_t* li, const float* p,
                                                              const float* u, float* ro, float* rd, float* att) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
@@ -201,8 +214,9 @@ static khp_status dbg_object_slots(khp_ctx* c, std::vector<uint32_t>& slot_of) {
 // Validates the (object, material) items of a BSDF query and resolves the objects' slots.
 static khp_status dbg_bsdf_items(khp_ctx* c, uint32_t n, const int32_t* obj, const int32_t* mat, uint32_t kinds_mask,
                                  std::vector<uint32_t>& slots) {
-    if (kinds_mask != KINDS_ALL && kinds_mask != KINDS_FUR)
-        return fail(KHP_EINVAL, "kinds_mask must be the full set or the fur set (Lambert + Marschner)");
+    if (kinds_mask != KINDS_ALL && kinds_mask != KINDS_FUR && kinds_mask != KINDS_ALL_HAIR && kinds_mask != KINDS_FUR_HAIR)
+        return fail(KHP_EINVAL, "kinds_mask must be the full set or the fur set (Lambert + Marschner), or, with "
+                                "ChiangHairBSDF, the twelve kinds or Lambert + ChiangHairBSDF");
     std::vector<uint32_t> slot_of;
     KHPCHK(dbg_object_slots(c, slot_of));
     slots.resize(n);
@@ -212,7 +226,7 @@ static khp_status dbg_bsdf_items(khp_ctx* c, uint32_t n, const int32_t* obj, con
         if (mat[i] < 0 || (size_t)mat[i] >= c->hs.mats.size())
             return fail(KHP_EINVAL, "item " + std::to_string(i) + ": material index out of range");
         const int32_t k = c->hs.mats[mat[i]].bsdf;
-        const uint32_t bit = (k >= 0 && k < KHP_BSDF_COUNT) ? (1u << k) : KINDS_ALL;
+        const uint32_t bit = (k >= 0 && k < KHP_BSDF_COUNT) ? (1u << k) : KINDS_ALL_HAIR;
         if (bit & ~kinds_mask)   // the instance has this case compiled out: never launch
             return fail(KHP_EINVAL, "item " + std::to_string(i) + ": BSDF kind " + std::to_string(k) +
                                         " is outside kinds_mask");
@@ -271,7 +285,12 @@ extern "C" khp_status khp_debug_bsdf_sample(khp_ctx* c, uint32_t n, uint32_t kin
     HIPCHK(os.ensure(8 * (size_t)n));
     HIPCHK(ofl.ensure(4 * (size_t)n));
     HIPCHK(ov.ensure(4 * (size_t)n));
-    if (kinds_mask == KINDS_FUR)
+    if (kinds_mask == KINDS_ALL_HAIR || kinds_mask == KINDS_FUR_HAIR)   // one covering instance, as the renderer's
+        hipLaunchKernelGGL(k_dbg_bsdf_sample<KINDS_ALL_HAIR>, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n,
+                           sl.as<uint32_t>(), mt.as<int32_t>(), di.as<float>(), dn.as<float>(), ds.as<float>(),
+                           dh.as<float>(), dfl.as<int32_t>(), od.as<float>(), op.as<float>(), of.as<float>(),
+                           os.as<float>(), ofl.as<int32_t>(), ov.as<int32_t>());
+    else if (kinds_mask == KINDS_FUR)
         hipLaunchKernelGGL(k_dbg_bsdf_sample<KINDS_FUR>, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n,
                            sl.as<uint32_t>(), mt.as<int32_t>(), di.as<float>(), dn.as<float>(), ds.as<float>(),
                            dh.as<float>(), dfl.as<int32_t>(), od.as<float>(), op.as<float>(), of.as<float>(),
@@ -340,7 +359,9 @@ extern "C" khp_status khp_debug_bsdf_eval(khp_ctx* c, uint32_t n, const int32_t*
                                           const float* in, const float* normal, const float* out, float* f) {
     KHPCHK(dbg_enter(c, n, obj && mat && in && normal && out && f));
     std::vector<uint32_t> slots;
-    KHPCHK(dbg_bsdf_items(c, n, obj, mat, KINDS_ALL, slots));
+    KHPCHK(dbg_bsdf_items(c, n, obj, mat, KINDS_ALL_HAIR, slots));
+    bool hair = false;
+    for (uint32_t i = 0; i < n; ++i) hair = hair || c->hs.mats[mat[i]].bsdf == KHP_BSDF_CHIANG_HAIR;
     DevMem sl, mt, di, dn, dout, of;
     HIPCHK(upload(sl, slots.data(), (size_t)n, c->stream));
     HIPCHK(upload(mt, mat, (size_t)n, c->stream));
@@ -348,8 +369,13 @@ extern "C" khp_status khp_debug_bsdf_eval(khp_ctx* c, uint32_t n, const int32_t*
     HIPCHK(upload(dn, normal, 3 * (size_t)n, c->stream));
     HIPCHK(upload(dout, out, 3 * (size_t)n, c->stream));
     HIPCHK(of.ensure(12 * (size_t)n));
-    hipLaunchKernelGGL(k_dbg_bsdf_eval, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n, sl.as<uint32_t>(),
-                       mt.as<int32_t>(), di.as<float>(), dn.as<float>(), dout.as<float>(), of.as<float>());
+    if (hair)
+        hipLaunchKernelGGL(k_dbg_bsdf_eval_hair, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n,
+                           sl.as<uint32_t>(), mt.as<int32_t>(), di.as<float>(), dn.as<float>(), dout.as<float>(),
+                           of.as<float>());
+    else
+        hipLaunchKernelGGL(k_dbg_bsdf_eval, dim3(dbg_grid(n)), dim3(DBG_BLOCK), 0, c->stream, c->S, n, sl.as<uint32_t>(),
+                           mt.as<int32_t>(), di.as<float>(), dn.as<float>(), dout.as<float>(), of.as<float>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(f, of.p, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     KHPCHK(wait_stream(c, c->stream, "the BSDF queries"));

@@ -9,6 +9,7 @@
 
 #include "kmath.h"
 #include "lens.h"
+#include "hair_pb.h"
 #include "scene.h"
 
 namespace khp {
@@ -400,22 +401,7 @@ __device__ __forceinline__ v3 light_emit(const DevLight& L, v3 dir) {
 // ---------------------------------------------------------------------------
 // BSDFs (Common/Shading/Bsdf.cpp)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float fresnel_dielectric(float cos_theta, float eta_i, float eta_t) {  // :143-171
-    float ci = gclamp(cos_theta, -1.0f, 1.0f);
-    if (ci <= 0.0f) {
-        float t = eta_i;
-        eta_i = eta_t;
-        eta_t = t;
-        ci = fabsf(ci);
-    }
-    float si = sqrtf(gmax(0.0f, 1.0f - ci * ci));
-    float st = eta_i / eta_t * si;
-    if (st >= 1.0f) return 1.0f;
-    float ct = sqrtf(gmax(0.0f, 1.0f - st * st));
-    float rparl = ((eta_t * ci) - (eta_i * ct)) / ((eta_t * ci) + (eta_i * ct));
-    float rperp = ((eta_i * ci) - (eta_t * ct)) / ((eta_i * ci) + (eta_t * ct));
-    return (rparl * rparl + rperp * rperp) / 2.0f;
-}
+// fresnel_dielectric (:143-171) is hair_pb.h's: the host entries of BSDF kind 11 compile it too.
 __device__ __forceinline__ v3 cosine_hemi(float u0, float u1) {  // :95-132
     float ox = 2.0f * u0 - 1.0f, oy = 2.0f * u1 - 1.0f, dx, dy;
     if (ox == 0.0f && oy == 0.0f) {
@@ -448,9 +434,19 @@ struct ShadeCtx {
     v3 U, V, W;   // hair frame (Object::getU/V/W): the cone's, or the fiber's for fur triangles
 };
 
-// BSDF::evaluateLight dispatch (Bsdf.cpp:197-202, 310-318, 771-776; others 0)
+// BSDF kind 11 (hair_pb.h) is compiled into the instances whose KINDS names it; the all-ones
+// default of KINDS predates the kind and means KIRK's eleven.
+template <uint32_t KINDS>
+constexpr bool kinds_chiang = KINDS != 0xFFFFFFFFu && (KINDS & (1u << KHP_BSDF_CHIANG_HAIR)) != 0u;
+
+// BSDF::evaluateLight dispatch (Bsdf.cpp:197-202, 310-318, 771-776; others 0); kind 11 gives
+// its true value f(w_o = out, w_i = in).
+template <uint32_t KINDS = 0xFFFFFFFFu>
 __device__ __forceinline__ v3 bsdf_eval(const ShadeCtx& s, v3 in, v3 out) {
     int kind = s.m->bsdf;
+    if constexpr (kinds_chiang<KINDS>) {
+        if (kind == KHP_BSDF_CHIANG_HAIR) return hair_pb_eval(*s.m, s.U, s.V, s.W, s.n, out, in);
+    }
     bool refl = dot(in, s.n) * dot(out, s.n) > 0.0f;
     v3 diff = mk(s.m->diffuse[0], s.m->diffuse[1], s.m->diffuse[2]);
     if (kind == KHP_BSDF_LAMBERTIAN_REFLECTION || kind == KHP_BSDF_MARSCHNER_HAIR)
@@ -551,6 +547,12 @@ v3 bsdf_sample(const ShadeCtx& s, v3 in, v3 n, float sample[2], float h0, float 
                                        float& pdf, int& flags, bool& valid, float lobe_u = 0.0f,
                                        uint32_t lobes = HAIR_LOBE_R) {
     v3 zero = mk(0.0f, 0.0f, 0.0f);
+    if constexpr (kinds_chiang<KINDS>) {   // hair_pb.h: u_l, u_n = sample[], u_0, u_1 = h0, h1; no early exit
+        if (s.m->bsdf == KHP_BSDF_CHIANG_HAIR) {
+            flags = 0;
+            return hair_pb_sample(*s.m, s.U, s.V, s.W, n, in, sample[0], sample[1], h0, h1, out, pdf, valid);
+        }
+    }
     valid = true;
     if (dot(in, n) == 0.0f) {
         valid = false;

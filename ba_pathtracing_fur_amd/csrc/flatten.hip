@@ -188,6 +188,15 @@ k_gen_fur(khp_fur_params p, uint32_t key0, uint32_t n_tris, uint32_t n_fibers, u
 
 static uint32_t blocks(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
 
+// BSDF kind 11 needs the cone's axis and radius: a triangle whose material is one is refused.
+// hair[m]: material m is of that kind.  A material index out of range is k_flatten_tris's to report.
+__global__ void k_check_hair_tris(const uint32_t* tm, uint32_t nt, const uint8_t* hair, uint32_t n_mat, uint32_t* err) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nt) return;
+    const uint32_t m = tm[i];
+    if (m < n_mat && hair[m]) atomicOr(err, 128u);
+}
+
 }  // namespace fl
 
 std::string device_flatten(const khp_scene* s, bool device_ptrs, uint32_t n_materials, bool textured,
@@ -275,6 +284,19 @@ std::string device_flatten(const khp_scene* s, bool device_ptrs, uint32_t n_mate
                            n_materials, o.rec.as<float4>(), o.aux.as<Aux>(), o.bounds.as<float>(),
                            o.centroid.as<float>(), textured ? o.cone_h.as<float>() : nullptr, err.as<uint32_t>());
     FLCHK(hipGetLastError());
+    DevMem dhair;
+    if (nt) {   // next to the material-index check: no triangle of a ChiangHairBSDF material
+        std::vector<uint8_t> hair(n_materials, 0);
+        bool any = false;
+        for (uint32_t m = 0; m < n_materials; ++m) any |= (hair[m] = s->materials[m].bsdf == KHP_BSDF_CHIANG_HAIR) != 0;
+        if (any) {
+            FLCHK(dhair.ensure(hair.size()));
+            FLCHK(hipMemcpyAsync(dhair.p, hair.data(), hair.size(), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_check_hair_tris, dim3(blocks(nt, 256)), dim3(256), 0, st, dtm, nt, dhair.as<uint8_t>(),
+                               n_materials, err.as<uint32_t>());
+            FLCHK(hipGetLastError());
+        }
+    }
     FLCHK(hipEventRecord(e1, st));
     uint32_t herr = 0;
     FLCHK(hipMemcpyAsync(&herr, err.p, 4, hipMemcpyDeviceToHost, st));
@@ -291,6 +313,7 @@ std::string device_flatten(const khp_scene* s, bool device_ptrs, uint32_t n_mate
     if (herr & 16u) return "EINVAL:cone_base_r0 holds a NaN or an infinity";
     if (herr & 32u) return "EINVAL:cone_apex_r1 holds a NaN or an infinity";
     if (herr & 64u) return "EINVAL:an object's bounds or centroid overflow float32";
+    if (herr & 128u) return "EINVAL:a triangle's material is a ChiangHairBSDF: the kind needs a cone's axis and radius";
     return std::string();
 }
 

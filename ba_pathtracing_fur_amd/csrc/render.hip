@@ -1160,6 +1160,27 @@ struct ShadeOut {
     v3 lc, Told, AT, ET;
     bool has_emit;
 };
+// BSDF kind 11 scatters from the whole fibre (hair_pb.h), so a ray that leaves the hit into
+// the fibre -- dot(w, n') < 0, n' the normal on the viewer's side -- starts beyond the cone's
+// far wall: rho is the hit's distance from the axis (surface_at's |q1 - base|), n_p the
+// normal's part at right angles to the axis, and the chord across the circle of radius rho
+// along w is 2 rho c / k.  Any other direction keeps the origin KIRK's rule gave it (org).
+__device__ __forceinline__ void hair_origin(const DevScene& S, int32_t slot, const ShadeCtx& s, v3 loc, v3 wo, v3 w,
+                                            v3& org) {
+    const v3 np = dot(wo, s.n) >= 0.0f ? s.n : -s.n;
+    if (!(dot(w, np) < 0.0f)) return;
+    const float4 c0 = S.prims[4 * (size_t)slot];
+    const float tt = dot(loc, s.V) - S.aux[slot].base_d;
+    const v3 q1 = loc - s.V * tt;
+    const float rho = length(q1 - mk(c0.x, c0.y, c0.z));
+    const v3 npp = normalize(np - s.V * dot(np, s.V));
+    const float c = -dot(w, npp);
+    const float dv = dot(w, s.V);
+    const float k = 1.0f - dv * dv;
+    const float tx = (k > 1e-8f) ? ((2.0f * rho) * c) / k : 0.0f;
+    org = loc + w * (tx * 1.001f + 1e-4f);
+}
+
 // NEE: next-event estimation towards one light, and the colour add that goes with it.  Without
 // it (the light-path variant) a surface hit whose colour term is due calls connect(s, loc, o, C)
 // in its place: k_shade's connection groups, which add the term to C or leave it to their finish.
@@ -1216,8 +1237,11 @@ __device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, floa
             v3 lightpos = h2l.o + h2l.d;
             h2l.o = h2l.o + faceforward(nrm, h2l.o - lightpos, nrm) * 1e-4f;
             h2l.d = normalize(h2l.d);
+            if constexpr (kinds_chiang<KINDS>) {
+                if (m->bsdf == KHP_BSDF_CHIANG_HAIR) hair_origin(S, slot, s, loc, counter, h2l.d, h2l.o);
+            }
             if (L.color[0] > 0.0f || L.color[1] > 0.0f || L.color[2] > 0.0f) {
-                v3 fe = bsdf_eval(s, h2l.d, -r.d);
+                v3 fe = bsdf_eval<KINDS>(s, h2l.d, -r.d);
                 float ad = fabsf(dot(h2l.d, nrm));
                 o.lc = mk(L.color[0] * ((att * fe.x) * ad), L.color[1] * ((att * fe.y) * ad),
                           L.color[2] * ((att * fe.z) * ad));
@@ -1227,6 +1251,9 @@ __device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, floa
             }
         }
         v3 ev = bsdf_eval(s, nrm, nrm);
+        if constexpr (kinds_chiang<KINDS>) {   // kind 11: KIRK's ambient term takes the fibre's colour
+            if (m->bsdf == KHP_BSDF_CHIANG_HAIR) ev = mk(m->diffuse[0], m->diffuse[1], m->diffuse[2]) * ONE_OVER_PI;
+        }
         v3 amb = mk(S.env.ambient[0], S.env.ambient[1], S.env.ambient[2]) * (ev * ONE_OVER_PI);
         o.Told = T;
         o.AT = amb * T;
@@ -1268,7 +1295,11 @@ __device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, floa
                 flags = fl;
                 v3 off = out * 1e-4f;
                 if ((fl & F_SPECULAR) != F_SPECULAR) off = faceforward(-(nrm * 1e-4f), nrm, out);
-                o.nr = make_ray(loc + off, out);
+                v3 org = loc + off;
+                if constexpr (kinds_chiang<KINDS>) {
+                    if (m->bsdf == KHP_BSDF_CHIANG_HAIR) hair_origin(S, slot, s, loc, counter, out, org);
+                }
+                o.nr = make_ray(org, out);
             }
         }
         if constexpr (!NEE) {
@@ -1435,12 +1466,16 @@ __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_s
 // BSDF kind sets k_shade and k_path are instantiated for: every kind, or the fur scenes'
 // (Lambert reflection + Marschner hair: configs 1-3 and the metric row), where
 // the other kinds' code and registers are compiled out.
-constexpr uint32_t KINDS_ALL = (1u << KHP_BSDF_COUNT) - 1u;
+constexpr uint32_t KINDS_ALL = 0x7FFu;   // KIRK's eleven kinds
+// Scenes with a kind-11 material (hair_pb.h) take one covering set: the eleven and ChiangHairBSDF.
+constexpr uint32_t KINDS_ALL_HAIR = (1u << KHP_BSDF_COUNT) - 1u;
+constexpr uint32_t KINDS_FUR_HAIR = (1u << KHP_BSDF_LAMBERTIAN_REFLECTION) | (1u << KHP_BSDF_CHIANG_HAIR);
+static_assert(KINDS_ALL_HAIR == 0xFFFu, "the covering set of scenes with kind 11");
 constexpr uint32_t KINDS_FUR = (1u << KHP_BSDF_LAMBERTIAN_REFLECTION) | (1u << KHP_BSDF_MARSCHNER_HAIR);
 // Host-side launch of the k_shade instance for (textured, light-path variant, fur-only scene, TT / TRT lobes);
 // grid_bd is the light-path instances' grid.  The lobe instances (never with the light-path variant) name their
 // kinds with KINDS_ALL; the others that keep every kind take k_shade's defaulted KINDS, a different instance.
-static void launch_shade(bool tex, bool bd, bool fur, bool lobes, int grid, int grid_bd, hipStream_t s,
+static void launch_shade(bool tex, bool bd, bool fur, bool lobes, bool hair, int grid, int grid_bd, hipStream_t s,
                          const DevScene& S, const Wave& W, int cur, uint32_t bounce) {
     constexpr uint32_t DEFAULTED = 0xFFFFFFFFu;
     // khp_set_lens: the lens twin, for the one launch that recomputes camera rays (never with the light-path variant)
@@ -1453,7 +1488,9 @@ static void launch_shade(bool tex, bool bd, bool fur, bool lobes, int grid, int 
             hipLaunchKernelGGL((k_shade<TEX, BD, K>), dim3(BD ? grid_bd : grid), dim3(shade_block<TEX, BD>()), 0, s, S, W, \
                                cur, bounce);                                                                           \
     } while (0)
-    if (lobes && tex) KHP_SHADE(true, false, KINDS_ALL | KINDS_LOBES);   // TT / TRT compiled in
+    if (hair && tex) KHP_SHADE(true, false, KINDS_ALL_HAIR);   // ChiangHairBSDF compiled in (never with bd or lobes)
+    else if (hair) KHP_SHADE(false, false, KINDS_ALL_HAIR);
+    else if (lobes && tex) KHP_SHADE(true, false, KINDS_ALL | KINDS_LOBES);   // TT / TRT compiled in
     else if (lobes && fur) KHP_SHADE(false, false, KINDS_FUR | KINDS_LOBES);
     else if (lobes) KHP_SHADE(false, false, KINDS_ALL | KINDS_LOBES);
     else if (tex && bd) KHP_SHADE(true, true, DEFAULTED);
@@ -2173,12 +2210,14 @@ static void launch_path_k(int grid, hipStream_t s, const DevScene& S, const Wave
     else hipLaunchKernelGGL((k_path<TEX, WIDE, K, false>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
 }
 // lobes: the instances with Marschner's TT / TRT paths compiled in (khp_set_hair_lobes)
-static void launch_path(bool tex, bool wide, bool fur, bool lobes, int grid, hipStream_t s, const DevScene& S,
+static void launch_path(bool tex, bool wide, bool fur, bool lobes, bool hair, int grid, hipStream_t s, const DevScene& S,
                         const Wave& W, SpillArea sp, const PathLanes& L, const Ahead& A, bool qs = false) {
 #define KHP_PATH(TEX, K)                                                    \
     (wide ? launch_path_k<TEX, true, K>(grid, s, S, W, sp, L, A, qs)        \
           : launch_path_k<TEX, false, K>(grid, s, S, W, sp, L, A, qs))
-    if (lobes && tex) KHP_PATH(true, KINDS_ALL | KINDS_LOBES);   // the ladder of launch_shade
+    if (hair && tex) KHP_PATH(true, KINDS_ALL_HAIR);   // the ladder of launch_shade
+    else if (hair) KHP_PATH(false, KINDS_ALL_HAIR);
+    else if (lobes && tex) KHP_PATH(true, KINDS_ALL | KINDS_LOBES);
     else if (lobes && fur) KHP_PATH(false, KINDS_FUR | KINDS_LOBES);
     else if (lobes) KHP_PATH(false, KINDS_ALL | KINDS_LOBES);
     else if (tex) KHP_PATH(true, KINDS_ALL);
@@ -3043,10 +3082,20 @@ extern "C" khp_status khp_get_bdpt(khp_ctx* c, khp_bdpt_params* out) {
     return KHP_OK;
 }
 
+// The scene in the context holds a material of BSDF kind 11 (hair_pb.h).
+static bool scene_has_chiang(const khp_ctx* c) {
+    if (!c->scene_set) return false;
+    for (const khp_material& m : c->hs.mats)
+        if (m.bsdf == KHP_BSDF_CHIANG_HAIR) return true;
+    return false;
+}
+
 extern "C" khp_status khp_set_bdpt(khp_ctx* c, const khp_bdpt_params* p) {
     if (!c || !p) return fail(KHP_EINVAL, "null argument");
     if (p->enabled && c->S.hair_lobes != HAIR_LOBE_R)
         return fail(KHP_EUNSUPPORTED, "the light-path variant traces the R lobe only: khp_set_hair_lobes(R) first");
+    if (p->enabled && scene_has_chiang(c))
+        return fail(KHP_EUNSUPPORTED, "the light-path variant does not trace ChiangHairBSDF materials: set a scene without them first");
     if (p->enabled && c->S.lens.radius > 0.0f)
         return fail(KHP_EUNSUPPORTED, "the light-path variant's image-plane stage assumes a pinhole sensor: khp_set_lens(radius 0) first");
     if (p->enabled && (p->light_paths < 1 || p->light_paths > 65536))
@@ -3079,6 +3128,8 @@ extern "C" khp_status khp_set_hair_lobes(khp_ctx* c, const khp_hair_lobes* p) {
     if (p->reserved != 0u) return fail(KHP_EINVAL, "reserved must be 0");
     if (p->lobes != KHP_HAIR_LOBE_R && c->bd.enabled)
         return fail(KHP_EUNSUPPORTED, "the light-path variant traces the R lobe only: disable khp_set_bdpt first");
+    if (p->lobes != KHP_HAIR_LOBE_R && scene_has_chiang(c))
+        return fail(KHP_EUNSUPPORTED, "TT / TRT lobes are Marschner's: the scene holds a ChiangHairBSDF material");
     HIPCHK(hipSetDevice(c->device));
     khp_status dr = drain(c);  // frames in flight finish with the lobes they started with
     if (dr != KHP_OK) return dr;
@@ -3226,6 +3277,12 @@ static khp_status set_scene_impl(khp_ctx* c, const khp_scene* s, bool device_ptr
         if (const char* f = device_table_field(s))
             return fail(KHP_EINVAL, std::string("khp_set_scene_device: ") + f + " must be host memory");
     }
+    if (s && s->materials && (c->bd.enabled || c->S.hair_lobes != HAIR_LOBE_R))   // refused before anything changes
+        for (uint32_t i = 0; i < s->n_materials; ++i)
+            if (s->materials[i].bsdf == KHP_BSDF_CHIANG_HAIR)
+                return fail(KHP_EUNSUPPORTED, c->bd.enabled
+                                                  ? "a ChiangHairBSDF material with the light-path variant enabled: disable khp_set_bdpt first"
+                                                  : "a ChiangHairBSDF material with hair lobes other than R: khp_set_hair_lobes(R) first");
     c->scene_set = false;
     c->built = false;
     ++c->gen;
@@ -3512,7 +3569,7 @@ extern "C" khp_status khp_build_accel(khp_ctx* c) {
     c->grid_sh_w = std::min(c->grid_sh, std::max(1, nb) * c->n_cu);  // the spill columns are sized by grid_sh
     c->bsdf_kinds = 0;   // the kinds the materials use: fur scenes run kernels with the others compiled out
     for (const khp_material& m : hs.mats)
-        c->bsdf_kinds |= (m.bsdf >= 0 && m.bsdf < KHP_BSDF_COUNT) ? (1u << m.bsdf) : KINDS_ALL;
+        c->bsdf_kinds |= (m.bsdf >= 0 && m.bsdf < KHP_BSDF_COUNT) ? (1u << m.bsdf) : KINDS_ALL_HAIR;
     nb = 0;
     if (S.textured) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_shade<true, false>), shade_block<true, false>(), 0));
     else if (fur_only(c))
@@ -3951,6 +4008,7 @@ struct BatchPlan {
     uint32_t hyb_from, rs_from;  // k_path takes over at this bounce (hybrid batches); ray sorting from this one (0: off)
     bool hyb_wide, ahead;        // ahead: render-ahead in the path kernel
     bool lobes_on, fur_only;     // khp_set_hair_lobes: the KINDS_LOBES instances; the KINDS_FUR instances
+    bool hair;                   // a ChiangHairBSDF material in the scene: the KINDS_ALL_HAIR instances
     bool overlap;                // the shadow stage on its own stream
     int grid_ext, grid_ext_w, grid_ext_cam, grid_sh, grid_sh_w, grid_path;   // this batch's share of the resident grids
 };
@@ -4057,6 +4115,7 @@ static khp_status plan_batch(khp_ctx* c, const khp_render_params* p, const std::
     pl.grid_path = std::max(1, ((pl.path_wide || pl.hyb_wide) ? c->grid_path_w : c->grid_path) / G);
     pl.lobes_on = c->S.hair_lobes != HAIR_LOBE_R;
     pl.fur_only = fur_only(c);
+    pl.hair = (c->bsdf_kinds & (1u << KHP_BSDF_CHIANG_HAIR)) != 0u;
     // Two streams: A runs generate / extend / shade / accumulate, B runs the
     // shadow stage (k_shadow + k_shadow_finish) of bounce b while A already
     // traverses bounce b+1, so each persistent kernel's tail fills with the
@@ -4255,7 +4314,7 @@ static khp_status enqueue_bounce(khp_ctx* c, const BatchPlan& pl, const khp_rend
         hipLaunchKernelGGL(k_hit_class, dim3(c->grid_shade), dim3(256), 0, sA, c->S, Wb, cur);
         hipLaunchKernelGGL(k_hit_scatter, dim3(c->grid_shade), dim3(256), 0, sA, Wb, cur);
     }
-    launch_shade(c->S.textured != 0, pl.bdm, pl.fur_only, pl.lobes_on, c->grid_shade, c->grid_shade_bd, sA, c->S, Wb,
+    launch_shade(c->S.textured != 0, pl.bdm, pl.fur_only, pl.lobes_on, pl.hair, c->grid_shade, c->grid_shade_bd, sA, c->S, Wb,
                  cur, b);
     timed(c, f, T_SHADE, false, sA);
     k.sorted = pl.rs_from > 0 && b + 1 >= pl.rs_from && b + 1 < p->depth;
@@ -4342,7 +4401,7 @@ static khp_status enqueue_chunk(khp_ctx* c, const BatchPlan& pl, const khp_rende
         HIPCHK(hipMemsetAsync(reinterpret_cast<char*>(Wv.cnt) + offsetof(Counters, fetch_ext), 0,
                               sizeof(Counters::fetch_ext), sA));
         timed(c, f, T_OTHER, true, sA);
-        launch_path(c->S.textured != 0, pl.path_wide, pl.fur_only, pl.lobes_on, pl.grid_path, sA, c->S, Wv, B.sp_path,
+        launch_path(c->S.textured != 0, pl.path_wide, pl.fur_only, pl.lobes_on, pl.hair, pl.grid_path, sA, c->S, Wv, B.sp_path,
                     B.PL, B.AH);
         HIPCHK(hipGetLastError());
         if (pl.ahead) ahead_commit(c, p, pl.call_paths);
@@ -4388,7 +4447,7 @@ static khp_status enqueue_chunk(khp_ctx* c, const BatchPlan& pl, const khp_rende
         if (!k.prepped) hipLaunchKernelGGL(k_prep, dim3(1), dim3(1), 0, sA, Wv.cnt, w.shqb.as<ShadowQ>() + cur, cur);
         c->cur_bounce = (int)pl.hyb_from;
         timed(c, f, T_OTHER, true, sA);
-        launch_path(c->S.textured != 0, pl.hyb_wide, pl.fur_only, pl.lobes_on, pl.grid_path, sA, c->S, Wq, B.sp_path,
+        launch_path(c->S.textured != 0, pl.hyb_wide, pl.fur_only, pl.lobes_on, pl.hair, pl.grid_path, sA, c->S, Wq, B.sp_path,
                     B.PL, Ahead{}, true);
         HIPCHK(hipGetLastError());
         timed(c, f, T_OTHER, false, sA);

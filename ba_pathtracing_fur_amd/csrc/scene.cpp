@@ -6,6 +6,7 @@
 #include "scene.h"
 #include "objects.h"
 #include "split_rule.h"
+#include "hair_pb.h"
 
 #include <string.h>
 
@@ -152,6 +153,8 @@ std::string flatten_scene(const khp_scene* s, HostScene& hs, bool objects) {
         const khp_material& m = s->materials[i];
         if (m.bsdf < 0 || m.bsdf >= KHP_BSDF_COUNT) return "unknown BSDF kind";
         if (m.shader < 0 || m.shader >= KHP_SHADER_COUNT) return "unknown shader kind";
+        if (m.bsdf == KHP_BSDF_CHIANG_HAIR)
+            if (const char* why = hair_material_error(m)) return "material " + std::to_string(i) + ": " + why;
     }
     for (uint32_t i = 0; i < s->n_lights; ++i)
         if (s->lights[i].kind < 0 || s->lights[i].kind > KHP_LIGHT_SUN) return "unknown light kind";
@@ -180,6 +183,9 @@ std::string flatten_scene(const khp_scene* s, HostScene& hs, bool objects) {
     else hs.tri_frame.assign(9 * (size_t)s->n_tris, 0.0f);
     for (uint32_t i = 0; i < s->n_tris; ++i)
         if (s->tri_mat[i] >= s->n_materials) return "triangle material index out of range";
+    for (uint32_t i = 0; i < s->n_tris; ++i)
+        if (s->materials[s->tri_mat[i]].bsdf == KHP_BSDF_CHIANG_HAIR)
+            return "a triangle's material is a ChiangHairBSDF: the kind needs a cone's axis and radius";
     for (uint32_t i = 0; i < s->n_cones; ++i)
         if (s->cone_mat[i] >= s->n_materials) return "cone material index out of range";
     if (s->cone_model)
@@ -607,7 +613,7 @@ extern "C" khp_status khp_gather_plan(uint32_t width, uint32_t height, uint32_t 
 static const char* kBsdfNames[KHP_BSDF_COUNT] = {
     "LambertianReflectionBSDF", "SpecularReflectionBSDF", "SpecularTransmissionBSDF", "GlossyBSDF",
     "GlassBSDF", "MilkGlassBSDF", "LambertianTransmissionBSDF", "EmissionBSDF", "TransparentBSDF",
-    "MarschnerHairBSDF", "DEonHairBSDF"};
+    "MarschnerHairBSDF", "DEonHairBSDF", "ChiangHairBSDF"};
 
 extern "C" int khp_bsdf_kind_from_name(const char* name) {
     if (!name) return -1;

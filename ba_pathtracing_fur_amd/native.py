@@ -22,7 +22,7 @@ STATUS_NAMES = {0: "KHP_OK", 1: "KHP_EINVAL", 2: "KHP_ENOMEM", 3: "KHP_EDEVICE",
 
 BSDF_NAMES = ["LambertianReflectionBSDF", "SpecularReflectionBSDF", "SpecularTransmissionBSDF", "GlossyBSDF",
               "GlassBSDF", "MilkGlassBSDF", "LambertianTransmissionBSDF", "EmissionBSDF", "TransparentBSDF",
-              "MarschnerHairBSDF", "DEonHairBSDF"]
+              "MarschnerHairBSDF", "DEonHairBSDF", "ChiangHairBSDF"]
 SHADER_NAMES = ["SimpleShader", "MarschnerHairShader"]
 LIGHT_POINT, LIGHT_QUAD, LIGHT_SPOT, LIGHT_SUN = 0, 1, 2, 3
 
@@ -357,7 +357,8 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_denoise_noise_defaults", "khp_denoise_var", "khp_denoise_var_host",
             "khp_reproject_params_defaults", "khp_reproject", "khp_reproject_host", "khp_debug_tex_color",
             "khp_debug_env_color", "khp_debug_material", "khp_lens_defaults", "khp_lens_from_kirk", "khp_set_lens",
-            "khp_get_lens", "khp_camera_rays_host", "khp_debug_camera_rays"]
+            "khp_get_lens", "khp_camera_rays_host", "khp_debug_camera_rays", "khp_hair_material",
+            "khp_hair_eval_host", "khp_hair_sample_host"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
 ABI_VERSION = 17
@@ -486,6 +487,11 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_lens_from_kirk": (c_int, [c_float, c_float, c_float, P(Lens)]),
         "khp_set_lens": (c_int, [c_void_p, P(Lens)]),
         "khp_get_lens": (c_int, [c_void_p, P(Lens)]),
+        "khp_hair_material": (c_int, [P(c_float), c_float, c_float, c_float, c_float, P(Material)]),
+        "khp_hair_eval_host": (c_int, [c_uint32, P(Material), P(c_float), P(c_float), P(c_float), P(c_float),
+                                       P(c_float)]),
+        "khp_hair_sample_host": (c_int, [c_uint32, P(Material), P(c_float), P(c_float), P(c_float), P(c_float),
+                                         P(c_float), P(c_float), P(c_float), P(c_int32)]),
         "khp_camera_rays_host": (c_int, [P(Camera), P(Lens), c_uint32, c_uint32, c_uint32, P(c_uint32), P(c_uint32),
                                          P(c_float), P(c_float)]),
         "khp_debug_camera_rays": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, P(c_uint32), P(c_uint32), P(c_float),

@@ -605,6 +605,8 @@ class HipContext:
     # ---- ABI 15 batch queries of the shading functions (test hooks) ----
     KINDS_ALL = (1 << 11) - 1          # every khp_bsdf_kind
     KINDS_FUR = (1 << 0) | (1 << 9)    # Lambert + Marschner: the set compiled for fur-only scenes
+    KINDS_ALL_HAIR = (1 << 12) - 1     # the eleven and ChiangHairBSDF: the set compiled for scenes with kind 11
+    KINDS_FUR_HAIR = (1 << 0) | (1 << 11)   # Lambert + ChiangHairBSDF (the same instance)
 
     def debug_surface(self, orig, direction):
         """khp_debug_surface: closest hit and the surface there, per ray."""
@@ -620,7 +622,8 @@ class HipContext:
         return r
 
     def debug_bsdf_sample(self, obj, mat, ray_in, normal, sample, hair, flags_in, kinds_mask=None):
-        """khp_debug_bsdf_sample on n items; kinds_mask: KINDS_ALL (default) or KINDS_FUR."""
+        """khp_debug_bsdf_sample on n items; kinds_mask: KINDS_ALL (default), KINDS_FUR, or, for items
+        of kind 11, KINDS_ALL_HAIR or KINDS_FUR_HAIR."""
         ob = np.ascontiguousarray(obj, np.int32).reshape(-1)
         n = len(ob)
         mt = np.ascontiguousarray(mat, np.int32).reshape(-1)
@@ -850,6 +853,45 @@ def camera_rays_host(camera: "N.Camera", width: int, pixels, samples, lens: dict
     N.check(lib, lib.khp_camera_rays_host(ctypes.byref(camera), prm, int(width), int(seed), len(px), N.uptr(px),
                                           N.uptr(sm), N.fptr(o), N.fptr(d)), "khp_camera_rays_host")
     return o, d
+
+
+def _hair_items(materials, n):
+    mats = list(materials) if not isinstance(materials, N.Material) else [materials]
+    if len(mats) == 1 and n > 1:
+        mats = mats * n
+    if len(mats) != n:
+        raise ValueError("one material, or one per item, is needed")
+    return (N.Material * n)(*mats)
+
+
+def hair_eval_host(materials, uvw, normal, wo, wi):
+    """khp_hair_eval_host: f(w_o, w_i) of ChiangHairBSDF materials (one, or one per item) in the hair
+    frames uvw (n, 3, 3), as a plain host loop over the kernels' own function -> f (n, 3)."""
+    lib = N.load_library()
+    fr = np.ascontiguousarray(uvw, np.float32).reshape(-1, 9)
+    n = len(fr)
+    nn, o, i = (np.ascontiguousarray(a, np.float32).reshape(n, 3) for a in (normal, wo, wi))
+    f = np.empty((n, 3), np.float32)
+    N.check(lib, lib.khp_hair_eval_host(n, _hair_items(materials, n), N.fptr(fr), N.fptr(nn), N.fptr(o), N.fptr(i),
+                                        N.fptr(f)), "khp_hair_eval_host")
+    return f
+
+
+def hair_sample_host(materials, uvw, normal, wo, draws):
+    """khp_hair_sample_host: one sample per item from the draws (n, 4) = u_l, u_n, u_0, u_1 -> a dict of
+    out (n, 3), pdf (n), f (n, 3) and valid (n)."""
+    lib = N.load_library()
+    fr = np.ascontiguousarray(uvw, np.float32).reshape(-1, 9)
+    n = len(fr)
+    nn, o = (np.ascontiguousarray(a, np.float32).reshape(n, 3) for a in (normal, wo))
+    u = np.ascontiguousarray(draws, np.float32).reshape(n, 4)
+    r = {"out": np.empty((n, 3), np.float32), "pdf": np.empty(n, np.float32), "f": np.empty((n, 3), np.float32),
+         "valid": np.empty(n, np.int32)}
+    N.check(lib, lib.khp_hair_sample_host(n, _hair_items(materials, n), N.fptr(fr), N.fptr(nn), N.fptr(o), N.fptr(u),
+                                          N.fptr(r["out"]), N.fptr(r["pdf"]), N.fptr(r["f"]),
+                                          r["valid"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+            "khp_hair_sample_host")
+    return r
 
 
 def _frame_check(name, a, width, height):

@@ -51,6 +51,18 @@ def fiber_material(bsdf="MarschnerHairBSDF") -> N.Material:
     return material(bsdf, "MarschnerHairShader", diffuse=FIBER_DIFFUSE, ior=FIBER_IOR)
 
 
+def hair_material(color, beta_m=0.3, beta_n=0.3, alpha=2.0, ior=1.55) -> N.Material:
+    """khp_hair_material: a ChiangHairBSDF fibre of colour `color` (each channel in (0, 1]): the
+    longitudinal and azimuthal roughness beta_m and beta_n in [0.01, 1], the cuticle tilt alpha in
+    degrees (|alpha| <= 30) and the index of refraction.  Cones only."""
+    lib = N.load_library()
+    c = np.ascontiguousarray(color, np.float32).reshape(3)
+    m = N.Material()
+    N.check(lib, lib.khp_hair_material(N.fptr(c), float(beta_m), float(beta_n), float(alpha), float(ior),
+                                       ctypes.byref(m)), "khp_hair_material")
+    return m
+
+
 def quad_light(position, direction, size, color, att_const=0.0, att_lin=0.0, att_quad=0.001) -> N.Light:
     """QuadLight ctor args (Light.h QuadLight defaults: const 0, lin 0, quad 0.001)."""
     L = N.Light()

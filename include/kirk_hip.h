@@ -61,7 +61,8 @@ typedef enum {
     KHP_BSDF_TRANSPARENT = 8,             /* "TransparentBSDF"            Bsdf.cpp:445-456 */
     KHP_BSDF_MARSCHNER_HAIR = 9,          /* "MarschnerHairBSDF"          Bsdf.cpp:465-776 */
     KHP_BSDF_DEON_HAIR = 10,              /* "DEonHairBSDF"               Bsdf.cpp:784-1056 */
-    KHP_BSDF_COUNT = 11
+    KHP_BSDF_CHIANG_HAIR = 11,            /* "ChiangHairBSDF": not KIRK's; khp_hair_material below */
+    KHP_BSDF_COUNT = 12
 } khp_bsdf_kind;
 
 typedef enum {
@@ -900,6 +901,42 @@ khp_status khp_camera_rays_host(const khp_camera* camera, const khp_lens* lens, 
 khp_status khp_debug_camera_rays(khp_ctx* ctx, uint32_t width, uint32_t seed, uint32_t n, const uint32_t* pixels,
                                  const uint32_t* samples, float* orig, float* dir);
 
+/* ---- an energy-conserving fibre: BSDF kind 11 (additive) -----------
+ * KIRK's two hair BSDFs are kept as written, with their faults, and
+ * next-event estimation treats them as Lambert.  KHP_BSDF_CHIANG_HAIR is the near-field
+ * fibre model of Chiang et al. 2016 beside them: four lobes (R, TT, TRT, residual),
+ * importance sampled from the four draws a hit already has, and evaluated towards the
+ * light with its true value.  A white fibre (sigma_a = 0) reflects and transmits all it
+ * receives.  Cones only: a triangle with such a material is KHP_EINVAL (no axis, no
+ * radius).  khp_material's fields are reused:
+ *   ior          eta                      roughness    beta_m (clamped to [0.01, 1] at use)
+ *   specular[0]  beta_n (clamped alike)   specular[1]  the cuticle tilt alpha, degrees
+ *   specular[2]  reserved, 0              volume       sigma_a per fibre diameter
+ *   diffuse      the colour of the albedo AOV and of KIRK's ambient term
+ *   shader       KHP_SHADER_SIMPLE
+ * A ray that leaves such a hit into the fibre starts beyond the fibre's far wall (the
+ * model scatters from the whole fibre); nothing else of the shading changes.  Scenes
+ * without the kind select the kernels they selected before and render the same bits.
+ * KHP_EUNSUPPORTED, in either order and changing nothing: a kind-11 material together
+ * with the light-path variant, or with hair lobes other than R.  No CPU oracle.
+ * khp_hair_material fills *out from a fibre colour (Chiang's colour map gives sigma_a);
+ * KHP_EINVAL: a null argument, color outside (0, 1], a beta outside [0.01, 1],
+ * |alpha_deg| > 30, ior not finite and > 1. */
+khp_status khp_hair_material(const float color[3], float beta_m, float beta_n, float alpha_deg, float ior,
+                             khp_material* out);
+/* The definition as plain host loops (no device, no context; csrc/hair_pb.h, compiled for
+ * the host and for gfx950: the same bits).  Item i: materials[i] (kind 11), the hair frame
+ * uvw[i] (U, V, W: 9 floats, V the axis), the normal, w_o (to the viewer) and w_i (to the
+ * light), 3 floats each, any length.  f [n][3] is the BSDF's value.  The sampler takes the
+ * draws u_l, u_n, u_0, u_1 ([n][4]) and gives the direction [n][3], its pdf [n], f [n][3]
+ * and valid [n] (0: a zero axis, or no energy to scatter; f and pdf are then 0).
+ * KHP_EINVAL: a null array, n outside [1, 2^20], a material of another kind. */
+khp_status khp_hair_eval_host(uint32_t n, const khp_material* materials, const float* uvw, const float* normal,
+                              const float* wo, const float* wi, float* f);
+khp_status khp_hair_sample_host(uint32_t n, const khp_material* materials, const float* uvw, const float* normal,
+                                const float* wo, const float* draws, float* out_dir, float* pdf, float* f,
+                                int32_t* valid);
+
 /* Completes every frame enqueued with KHP_RENDER_ASYNC (ABI 5).  A progressive
  * caller (KIRK's PathTracer::render loop) enqueues its passes and syncs before
  * reading the texture; passes accumulate in call order.  Any synchronous call
@@ -1102,9 +1139,12 @@ khp_status khp_debug_surface(khp_ctx* ctx, uint32_t n, const float* orig, const 
 /* BSDF::sample of material[i] (index into the scene's materials, untextured)
  * at a synthetic hit on object[i] (its hair frame), for ray_in in[i], normal
  * n[i], sample[i][2], the two hair draws hair[i][2] and the incoming flags.
- * kinds_mask selects the compiled instance: (1 << KHP_BSDF_COUNT) - 1 for all
- * kinds, or (1 << LAMBERTIAN_REFLECTION) | (1 << MARSCHNER_HAIR), the set the
- * renderer compiles for fur-only scenes; any other mask, or an item whose
+ * kinds_mask selects the compiled instance: 0x7FF for KIRK's eleven kinds, or
+ * (1 << LAMBERTIAN_REFLECTION) | (1 << MARSCHNER_HAIR), the set the renderer
+ * compiles for fur-only scenes; (1 << 12) - 1 or (1 << LAMBERTIAN_REFLECTION) |
+ * (1 << CHIANG_HAIR) for the instance with kind 11 compiled in (a kind-11 item
+ * takes sample[i] as u_l, u_n and hair[i] as u_0, u_1, and has no early exit;
+ * the two sets select the same instance); any other mask, or an item whose
  * material's kind is outside the mask, is KHP_EINVAL (the instance has that
  * case compiled out).  Outputs: direction [n][3], pdf [n], f [n][3], the sample
  * as written back [n][2], flags [n], valid [n] (0: the dot(in, n) == 0 early
@@ -1125,7 +1165,8 @@ khp_status khp_debug_hair_sample(khp_ctx* ctx, uint32_t n, uint32_t lobes, const
                                  const int32_t* material, const float* in, const float* normal, const float* hair,
                                  const float* lobe_u, const int32_t* flags_in, float* out_dir, float* pdf, float* f,
                                  float* sample_out, int32_t* flags_out, int32_t* valid);
-/* BSDF::evaluateLight for the same kind of item and the direction out[i]: f [n][3]. */
+/* BSDF::evaluateLight for the same kind of item and the direction out[i]: f [n][3].
+ * An item of kind 11 gives the fibre model's value f(w_o = out[i], w_i = in[i]). */
 khp_status khp_debug_bsdf_eval(khp_ctx* ctx, uint32_t n, const int32_t* object, const int32_t* material,
                                const float* in, const float* normal, const float* out, float* f);
 /* Light::calcLightdir (randomize = true) of light[i] from point[i] with the

@@ -292,4 +292,12 @@ inline khp_material material(int bsdf, int shader, const float diffuse[3], float
     return m;
 }
 
+// A ChiangHairBSDF fibre of colour `color` (khp_hair_material): kind 11, for cones only
+inline khp_material hair_material(const float color[3], float beta_m = 0.3f, float beta_n = 0.3f, float alpha_deg = 2.0f,
+                                  float ior = 1.55f) {
+    khp_material m{};
+    check(khp_hair_material(color, beta_m, beta_n, alpha_deg, ior, &m), "khp_hair_material");
+    return m;
+}
+
 }  // namespace khp
