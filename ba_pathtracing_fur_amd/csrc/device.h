@@ -10,6 +10,7 @@
 #include "kmath.h"
 #include "lens.h"
 #include "hair_pb.h"
+#include "env_light.h"
 #include "scene.h"
 
 namespace khp {
@@ -50,6 +51,7 @@ struct DevScene {
     int32_t top_root;
     uint32_t hair_lobes;   // khp_set_hair_lobes: KHP_HAIR_LOBE_* bits, read by KINDS_LOBES instances only
     khp_lens lens;         // khp_set_lens: radius 0 (the default) is the pinhole camera (lens.h)
+    const EnvLight* __restrict__ envl;   // khp_set_env_light: the map and its table, read by ENV instances only; null: off
 };
 
 // ---- textures (ABI 6) -------------------------------------------------------------------

@@ -1184,7 +1184,11 @@ __device__ __forceinline__ void hair_origin(const DevScene& S, int32_t slot, con
 // NEE: next-event estimation towards one light, and the colour add that goes with it.  Without
 // it (the light-path variant) a surface hit whose colour term is due calls connect(s, loc, o, C)
 // in its place: k_shade's connection groups, which add the term to C or leave it to their finish.
-template <bool TEX, uint32_t KINDS, bool NEE = true, class Connect = std::nullptr_t>
+// ENV: the instances behind khp_set_env_light (S.envl set; the plan picks them, as it picks the
+// lens instances): a hit of a kind whose bsdf_eval can be non-zero may aim its one shadow ray at
+// the map instead of a light, and an escaping ray adds the map's radiance, not env.color, where
+// no such ray stood in for it (env_light.h).  Without ENV none of it is compiled.
+template <bool TEX, uint32_t KINDS, bool NEE = true, bool ENV = false, class Connect = std::nullptr_t>
 __device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, float lambda, int32_t slot, v3 T, v3 C,
                                            int flags, uint32_t key, uint32_t bounce, bool last, ShadeOut& o,
                                            Connect connect = nullptr) {
@@ -1210,7 +1214,19 @@ __device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, floa
         light_hit = true;
     }
     if (lambda == FLT_MAX_) {  // EnvironmentShader::shade
-        C = C + (TEX ? env_color(S, r.d) : mk(S.env.color[0], S.env.color[1], S.env.color[2])) * T;
+        if constexpr (ENV) {
+            // the map is added where no next-event ray of the previous hit stood in for it
+            const EnvLight E = *S.envl;
+            if (E.nee == 0u || bounce == 0u || !(flags & F_ENV_NEE)) {
+                v3 Le;
+                float pe;
+                uint32_t te;
+                env_light_eval(E, r.d, Le, pe, te);
+                C = C + Le * T;
+            }
+        } else {
+            C = C + (TEX ? env_color(S, r.d) : mk(S.env.color[0], S.env.color[1], S.env.color[2])) * T;
+        }
         T = mk(0, 0, 0);
     } else if (light_hit) {    // LightShader::shade
         C = C + light_emit(S.lights[t_index], r.d) * T;
@@ -1228,8 +1244,61 @@ __device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, floa
         // NEE setup: SimpleShader::calcDirectLight (SimpleShader.h:101-152) and
         // MarschnerHairShader::calcDirectLight (MarschnerHairShader.h:87-138)
         bool need_shadow = false;
-        if (NEE && S.n_lights > 0) {
-            int li = (int)((double)draw_u01(key, dim_of(bounce, P_LIGHT_SEL)) * (double)S.n_lights);
+        // ENV: the hit's one shadow ray goes to the map (env_sel), or to a light chosen from the
+        // rescaled draw, its term times lscale = 1 / (1 - select)
+        [[maybe_unused]] float u_sel = 0.0f, lscale = 1.0f;
+        [[maybe_unused]] bool env_kind = false, env_sel = false;
+        if constexpr (ENV && NEE) {
+            u_sel = draw_u01(key, dim_of(bounce, P_LIGHT_SEL));
+            const int kind = m->bsdf;
+            // (not at the last bounce: a ray that escapes after this hit is not traced, so the map's light
+            // after `depth` hits is outside the integral with nee = 0, and stays outside it with nee = 1)
+            env_kind = S.envl->nee != 0u && !last &&
+                       (kind == KHP_BSDF_LAMBERTIAN_REFLECTION || kind == KHP_BSDF_LAMBERTIAN_TRANSMISSION ||
+                        kind == KHP_BSDF_MARSCHNER_HAIR || kind == KHP_BSDF_CHIANG_HAIR);
+            if (env_kind) {
+                const float sel = S.envl->select;
+                float wsel = 1.0f;
+                if (S.n_lights == 0) {
+                    env_sel = true;
+                } else if (u_sel < sel) {
+                    env_sel = true;
+                    wsel = 1.0f / sel;
+                } else {
+                    const float rest = 1.0f - sel;
+                    u_sel = gmin((u_sel - sel) / rest, ENV_BELOW_ONE);   // (a rounded quotient may reach 1)
+                    lscale = 1.0f / rest;
+                }
+                if (env_sel) {
+                    const EnvLight E = *S.envl;
+                    v3 d, Le;
+                    float pe;
+                    uint32_t te;
+                    bool ok;
+                    env_light_sample(E, draw_u01(key, dim_of(bounce, P_LIGHT_0)), draw_u01(key, dim_of(bounce, P_LIGHT_1)),
+                                     d, Le, pe, te, ok);
+                    if (ok) {
+                        Ray h2l;
+                        h2l.o = loc + faceforward(nrm, -d, nrm) * 1e-4f;
+                        h2l.d = d;
+                        if constexpr (kinds_chiang<KINDS>) {
+                            if (kind == KHP_BSDF_CHIANG_HAIR) hair_origin(S, slot, s, loc, counter, h2l.d, h2l.o);
+                        }
+                        const v3 fe = bsdf_eval<KINDS>(s, h2l.d, -r.d);
+                        const float ad = fabsf(dot(h2l.d, nrm));
+                        o.lc = mk(Le.x * (((fe.x * ad) / pe) * wsel), Le.y * (((fe.y * ad) / pe) * wsel),
+                                  Le.z * (((fe.z * ad) / pe) * wsel));
+                        o.sh_tmax = FLT_MAX_;
+                        o.shr = h2l;
+                        need_shadow = true;
+                    }
+                }
+            }
+        }
+        if (NEE && S.n_lights > 0 && !(ENV && env_sel)) {
+            int li;
+            if constexpr (ENV && NEE) li = (int)((double)u_sel * (double)S.n_lights);
+            else li = (int)((double)draw_u01(key, dim_of(bounce, P_LIGHT_SEL)) * (double)S.n_lights);
             const DevLight& L = S.lights[li];
             float att;
             Ray h2l = light_dir(L, loc, draw_u01(key, dim_of(bounce, P_LIGHT_0)),
@@ -1245,6 +1314,7 @@ __device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, floa
                 float ad = fabsf(dot(h2l.d, nrm));
                 o.lc = mk(L.color[0] * ((att * fe.x) * ad), L.color[1] * ((att * fe.y) * ad),
                           L.color[2] * ((att * fe.z) * ad));
+                if constexpr (ENV) o.lc = o.lc * lscale;
                 o.sh_tmax = length(lightpos - h2l.o);
                 o.shr = h2l;
                 need_shadow = true;
@@ -1317,6 +1387,8 @@ __device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, floa
                 C = C + deferred_add(mk(0, 0, 0), o.Told, o.AT, o.has_emit, o.ET);
             }
         }
+        // the path leaves the hit with F_ENV_NEE iff a next-event ray could stand in for the map here
+        if constexpr (ENV) flags = (flags & ~(int)F_ENV_NEE) | (env_kind ? (int)F_ENV_NEE : 0);
     }
     o.T = T;
     o.C = C;
@@ -1330,7 +1402,8 @@ __device__ __forceinline__ void shade_core(const DevScene& S, const Ray& r, floa
 #define KHP_SHADE_WAVES 1   // min waves per SIMD for k_shade's register budget (1: unconstrained)
 #endif
 // LENS: bounce 0's recomputed camera rays are lens rays (khp_set_lens; launched for that bounce only).
-template <bool TEX, bool BD, uint32_t KINDS = 0xFFFFFFFFu, bool LENS = false>
+// ENV: shade_core's environment-light instance (khp_set_env_light; never with the light-path variant).
+template <bool TEX, bool BD, uint32_t KINDS = 0xFFFFFFFFu, bool LENS = false, bool ENV = false>
 __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_shade(DevScene S, Wave Wv, int cur, uint32_t bounce) {
     const uint32_t nf = Wv.cnt->nq[cur], n = nf + Wv.cnt->nqb[cur];
     const int nxt = cur ^ 1;
@@ -1417,7 +1490,7 @@ __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_s
                     }
                 }
             };
-            shade_core<TEX, KINDS, !BD>(S, r, Wv.ht[i], Wv.hslot[i], mk(tf.x, tf.y, tf.z), mk(ck.x, ck.y, ck.z),
+            shade_core<TEX, KINDS, !BD, ENV>(S, r, Wv.ht[i], Wv.hslot[i], mk(tf.x, tf.y, tf.z), mk(ck.x, ck.y, ck.z),
                                         (int)bits_from_f(tf.w), key, bounce, last, so, connect);
             // (with a deferred add -- emit_sh or a BD group -- C is unchanged here and the
             // shadow finish adds this bounce's term to wherever the state goes)
@@ -1488,6 +1561,21 @@ static void launch_shade(bool tex, bool bd, bool fur, bool lobes, bool hair, int
             hipLaunchKernelGGL((k_shade<TEX, BD, K>), dim3(BD ? grid_bd : grid), dim3(shade_block<TEX, BD>()), 0, s, S, W, \
                                cur, bounce);                                                                           \
     } while (0)
+    if (S.envl) {   // khp_set_env_light: the covering kind set with the light compiled in (never with bd or lobes)
+#define KHP_SHADE_ENV(TEX)                                                                                             \
+    do {                                                                                                               \
+        if (lens)                                                                                                      \
+            hipLaunchKernelGGL((k_shade<TEX, false, KINDS_ALL_HAIR, true, true>), dim3(grid),                          \
+                               dim3(shade_block<TEX, false>()), 0, s, S, W, cur, bounce);                              \
+        else                                                                                                           \
+            hipLaunchKernelGGL((k_shade<TEX, false, KINDS_ALL_HAIR, false, true>), dim3(grid),                         \
+                               dim3(shade_block<TEX, false>()), 0, s, S, W, cur, bounce);                              \
+    } while (0)
+        if (tex) KHP_SHADE_ENV(true);
+        else KHP_SHADE_ENV(false);
+#undef KHP_SHADE_ENV
+        return;
+    }
     if (hair && tex) KHP_SHADE(true, false, KINDS_ALL_HAIR);   // ChiangHairBSDF compiled in (never with bd or lobes)
     else if (hair) KHP_SHADE(false, false, KINDS_ALL_HAIR);
     else if (lobes && tex) KHP_SHADE(true, false, KINDS_ALL | KINDS_LOBES);   // TT / TRT compiled in
@@ -1852,7 +1940,8 @@ __device__ unsigned long long g_ra_prof[2];
 // carries them through the remaining bounces; paths of a chunk that ended earlier
 // already wrote their colour.
 // LENS (never with QS, whose launches make no camera ray): the camera rays are lens rays (khp_set_lens).
-template <bool TEX, bool WIDE, uint32_t KINDS, bool RA, bool QS = false, bool LENS = false>
+// ENV: shade_core's environment-light instance (khp_set_env_light).
+template <bool TEX, bool WIDE, uint32_t KINDS, bool RA, bool QS = false, bool LENS = false, bool ENV = false>
 __global__ __launch_bounds__(TRAV_BLOCK, PATH_WAVES) void k_path(DevScene S, Wave Wv, SpillArea spill, PathLanes L, Ahead A) {
     extern __shared__ uint32_t lds[];
     const uint32_t npaths = Wv.P * Wv.n_samples * Wv.n_frames;
@@ -1920,7 +2009,7 @@ __global__ __launch_bounds__(TRAV_BLOCK, PATH_WAVES) void k_path(DevScene S, Wav
                     const float4 f0 = L.col[0][g], f1 = L.col[1][g], f2 = L.col[2][g], f3 = L.col[3][g];
                     const uint32_t bounce = bits_from_f(f3.w) & 0xFFFFu;
                     ShadeOut o;
-                    shade_core<TEX, KINDS>(S, fr, h.t, h.slot, mk(f0.x, f0.y, f0.z), mk(f1.x, f1.y, f1.z),
+                    shade_core<TEX, KINDS, true, ENV>(S, fr, h.t, h.slot, mk(f0.x, f0.y, f0.z), mk(f1.x, f1.y, f1.z),
                                            (int)bits_from_f(f0.w), bits_from_f(f1.w), bounce, bounce + 1 >= Wv.depth, o);
                     ++n_ext;
                     const float4 tfo = make_float4(o.T.x, o.T.y, o.T.z, f_from_bits((uint32_t)o.flags));
@@ -2194,9 +2283,18 @@ __global__ __launch_bounds__(TRAV_BLOCK, PATH_WAVES) void k_path(DevScene S, Wav
 }
 
 constexpr size_t PATH_LDS = PATH_LDS_BYTES;
-template <bool TEX, bool WIDE, uint32_t K>
+template <bool TEX, bool WIDE, uint32_t K, bool ENV = false>
 static void launch_path_k(int grid, hipStream_t s, const DevScene& S, const Wave& W, SpillArea sp, const PathLanes& L,
                           const Ahead& A, bool qs) {
+    if constexpr (ENV) {   // khp_set_env_light: the twins of the launches below
+        const dim3 g(grid), b(TRAV_BLOCK);
+        if (qs) hipLaunchKernelGGL((k_path<TEX, WIDE, K, false, true, false, true>), g, b, PATH_LDS, s, S, W, sp, L, A);
+        else if (S.lens.radius > 0.0f && A.on) hipLaunchKernelGGL((k_path<TEX, WIDE, K, true, false, true, true>), g, b, PATH_LDS, s, S, W, sp, L, A);
+        else if (S.lens.radius > 0.0f) hipLaunchKernelGGL((k_path<TEX, WIDE, K, false, false, true, true>), g, b, PATH_LDS, s, S, W, sp, L, A);
+        else if (A.on) hipLaunchKernelGGL((k_path<TEX, WIDE, K, true, false, false, true>), g, b, PATH_LDS, s, S, W, sp, L, A);
+        else hipLaunchKernelGGL((k_path<TEX, WIDE, K, false, false, false, true>), g, b, PATH_LDS, s, S, W, sp, L, A);
+        return;
+    }
     if (qs) {
         hipLaunchKernelGGL((k_path<TEX, WIDE, K, false, true>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
         return;
@@ -2215,6 +2313,13 @@ static void launch_path(bool tex, bool wide, bool fur, bool lobes, bool hair, in
 #define KHP_PATH(TEX, K)                                                    \
     (wide ? launch_path_k<TEX, true, K>(grid, s, S, W, sp, L, A, qs)        \
           : launch_path_k<TEX, false, K>(grid, s, S, W, sp, L, A, qs))
+    if (S.envl) {   // khp_set_env_light: the covering kind set with the light compiled in
+        if (tex) (wide ? launch_path_k<true, true, KINDS_ALL_HAIR, true>(grid, s, S, W, sp, L, A, qs)
+                       : launch_path_k<true, false, KINDS_ALL_HAIR, true>(grid, s, S, W, sp, L, A, qs));
+        else (wide ? launch_path_k<false, true, KINDS_ALL_HAIR, true>(grid, s, S, W, sp, L, A, qs)
+                   : launch_path_k<false, false, KINDS_ALL_HAIR, true>(grid, s, S, W, sp, L, A, qs));
+        return;
+    }
     if (hair && tex) KHP_PATH(true, KINDS_ALL_HAIR);   // the ladder of launch_shade
     else if (hair) KHP_PATH(false, KINDS_ALL_HAIR);
     else if (lobes && tex) KHP_PATH(true, KINDS_ALL | KINDS_LOBES);
@@ -2742,6 +2847,9 @@ struct khp_ctx {
     int grid_sh_w = 0;     // k_shadow on the two-level records
     int grid_path = 0, grid_path_w = 0;   // k_path (64-B / two-level records)
     uint32_t bsdf_kinds = 0;              // the BSDF kinds the scene's materials use (bit per khp_bsdf_kind)
+    // khp_set_env_light: the parameters (rgb null), the map, its table and the EnvLight record S.envl points at
+    khp_env_light env_light{};
+    DevMem envl_rgb, envl_weight, envl_row_cdf, envl_marginal, envl_dev;
     // (khp_set_hair_lobes keeps its mask in S.hair_lobes, khp_set_lens its lens in S.lens: the
     // scene build leaves both alone)
     int grid_ext_max = 0;  // the k_extend spill columns are sized for the largest grid
@@ -3098,6 +3206,8 @@ extern "C" khp_status khp_set_bdpt(khp_ctx* c, const khp_bdpt_params* p) {
         return fail(KHP_EUNSUPPORTED, "the light-path variant does not trace ChiangHairBSDF materials: set a scene without them first");
     if (p->enabled && c->S.lens.radius > 0.0f)
         return fail(KHP_EUNSUPPORTED, "the light-path variant's image-plane stage assumes a pinhole sensor: khp_set_lens(radius 0) first");
+    if (p->enabled && c->S.envl)
+        return fail(KHP_EUNSUPPORTED, "the light-path variant knows KIRK's lights only: turn khp_set_env_light off first");
     if (p->enabled && (p->light_paths < 1 || p->light_paths > 65536))
         return fail(KHP_EINVAL, "light_paths must be 1..65536");
     if (p->enabled && (p->vertices < 1 || p->vertices > 16)) return fail(KHP_EINVAL, "vertices must be 1..16");
@@ -3130,6 +3240,8 @@ extern "C" khp_status khp_set_hair_lobes(khp_ctx* c, const khp_hair_lobes* p) {
         return fail(KHP_EUNSUPPORTED, "the light-path variant traces the R lobe only: disable khp_set_bdpt first");
     if (p->lobes != KHP_HAIR_LOBE_R && scene_has_chiang(c))
         return fail(KHP_EUNSUPPORTED, "TT / TRT lobes are Marschner's: the scene holds a ChiangHairBSDF material");
+    if (p->lobes != KHP_HAIR_LOBE_R && c->S.envl)
+        return fail(KHP_EUNSUPPORTED, "TT / TRT lobes are not traced under the environment light: turn khp_set_env_light off first");
     HIPCHK(hipSetDevice(c->device));
     khp_status dr = drain(c);  // frames in flight finish with the lobes they started with
     if (dr != KHP_OK) return dr;
@@ -3183,6 +3295,7 @@ extern "C" khp_status khp_create(khp_ctx** out, int device, uint32_t flags) {
     khp_bdpt_params_defaults(&c->bd);
     c->S.hair_lobes = HAIR_LOBE_R;
     khp_lens_defaults(&c->S.lens);
+    khp_env_light_defaults(&c->env_light);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -5131,6 +5244,7 @@ extern "C" khp_status khp_debug_queue(khp_ctx* c, uint32_t* n, float* orig, floa
 }
 
 #include "debug_query.h"   // ABI 15: khp_debug_surface / _bsdf_sample / _bsdf_eval / _light_dir / _light_isect
+#include "env_light_dev.h" // khp_set_env_light: the table build, the entry points and their queries
 #include "aov.h"           // khp_render_aov: per-pixel first-hit feature buffers
 #include "denoise_dev.h"   // khp_denoise: the guided a-trous filter over those buffers
 #include "denoise_var_dev.h"   // khp_denoise_var: the same filter guided by measured variance

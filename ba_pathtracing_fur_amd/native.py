@@ -160,6 +160,19 @@ class Lens(ctypes.Structure):
         return {"radius": float(self.radius), "focus_distance": float(self.focus_distance), "focus": int(self.focus)}
 
 
+ENV_LIGHT_DEVICE = 1
+
+
+class EnvLight(ctypes.Structure):
+    """khp_env_light (40 bytes): a latitude-longitude map of float32 radiance as a light; 0 x 0 is off."""
+    _fields_ = [("width", c_uint32), ("height", c_uint32), ("flags", c_uint32), ("nee", c_uint32), ("scale", c_float),
+                ("rotation", c_float), ("select", c_float), ("reserved", c_uint32), ("rgb", c_void_p)]
+
+    def as_dict(self) -> dict:
+        return {"width": int(self.width), "height": int(self.height), "nee": bool(self.nee), "scale": float(self.scale),
+                "rotation": float(self.rotation), "select": float(self.select)}
+
+
 class AovBuffers(ctypes.Structure):
     """khp_aov_buffers (48 bytes): the planes khp_render_aov writes; a null plane is not computed."""
     _fields_ = [("normal", POINTER(c_float)), ("albedo", POINTER(c_float)), ("tangent", POINTER(c_float)),
@@ -358,7 +371,9 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_reproject_params_defaults", "khp_reproject", "khp_reproject_host", "khp_debug_tex_color",
             "khp_debug_env_color", "khp_debug_material", "khp_lens_defaults", "khp_lens_from_kirk", "khp_set_lens",
             "khp_get_lens", "khp_camera_rays_host", "khp_debug_camera_rays", "khp_hair_material",
-            "khp_hair_eval_host", "khp_hair_sample_host"]
+            "khp_hair_eval_host", "khp_hair_sample_host", "khp_env_light_defaults", "khp_set_env_light",
+            "khp_get_env_light", "khp_env_light_tables_host", "khp_env_light_sample_host", "khp_env_light_eval_host",
+            "khp_debug_env_light_tables", "khp_debug_env_light"]
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
 ABI_VERSION = 17
@@ -496,6 +511,16 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
                                          P(c_float), P(c_float)]),
         "khp_debug_camera_rays": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, P(c_uint32), P(c_uint32), P(c_float),
                                           P(c_float)]),
+        "khp_env_light_defaults": (None, [P(EnvLight)]),
+        "khp_set_env_light": (c_int, [c_void_p, P(EnvLight)]),
+        "khp_get_env_light": (c_int, [c_void_p, P(EnvLight)]),
+        "khp_env_light_tables_host": (c_int, [P(EnvLight), P(c_uint32), P(c_uint32), P(ctypes.c_uint64)]),
+        "khp_env_light_sample_host": (c_int, [P(EnvLight), c_uint32, P(c_float), P(c_float), P(c_float), P(c_float),
+                                              P(c_int32)]),
+        "khp_env_light_eval_host": (c_int, [P(EnvLight), c_uint32, P(c_float), P(c_float), P(c_float)]),
+        "khp_debug_env_light_tables": (c_int, [c_void_p, P(c_uint32), P(c_uint32), P(ctypes.c_uint64)]),
+        "khp_debug_env_light": (c_int, [c_void_p, c_uint32, P(c_float), P(c_float), P(c_float), P(c_float), P(c_float),
+                                        P(c_int32), P(c_float), P(c_float)]),
         "khp_debug_hair_sample": (c_int, [c_void_p, c_uint32, c_uint32, P(c_int32), P(c_int32), P(c_float), P(c_float),
                                           P(c_float), P(c_float), P(c_int32), P(c_float), P(c_float), P(c_float),
                                           P(c_float), P(c_int32), P(c_int32)]),

@@ -248,6 +248,56 @@ class HipContext:
         N.check(self.lib, self.lib.khp_get_lens(self.ptr, ctypes.byref(prm)), "khp_get_lens")
         return prm.as_dict()
 
+    def set_env_light(self, rgb, scale: float = 1.0, rotation: float = 0.0, nee: bool = True, select: float = 0.5,
+                      device_shape=None) -> None:
+        """khp_set_env_light: light the next renders by a latitude-longitude map of float32 radiance,
+        rgb (height, width, 3), row 0 the -y pole.  The map is copied and its sampling table built on the
+        device; nee=False leaves the map to escaping rays alone; select is the chance that a hit's one
+        shadow ray goes to the map when the scene also has lights.  rgb may be a device address (int) of
+        this context's GPU with device_shape = (height, width)."""
+        if device_shape is not None:
+            h, w = (int(v) for v in device_shape)
+            prm = N.EnvLight(w, h, N.ENV_LIGHT_DEVICE, int(bool(nee)), float(scale), float(rotation), float(select), 0,
+                             rgb.ptr if isinstance(rgb, DeviceBuffer) else int(rgb))
+        else:
+            prm, _keep = _env_light_arg(rgb, scale, rotation, nee, select)
+        N.check(self.lib, self.lib.khp_set_env_light(self.ptr, ctypes.byref(prm)), "khp_set_env_light")
+
+    def clear_env_light(self) -> None:
+        """khp_set_env_light with a 0 x 0 map: the context's renders are KIRK's again."""
+        prm = N.EnvLight()
+        self.lib.khp_env_light_defaults(ctypes.byref(prm))
+        N.check(self.lib, self.lib.khp_set_env_light(self.ptr, ctypes.byref(prm)), "khp_set_env_light")
+
+    def env_light(self) -> dict:
+        """khp_get_env_light: width, height (0 x 0: off), nee, scale, rotation and select."""
+        prm = N.EnvLight()
+        N.check(self.lib, self.lib.khp_get_env_light(self.ptr, ctypes.byref(prm)), "khp_get_env_light")
+        return prm.as_dict()
+
+    def debug_env_light_tables(self) -> dict:
+        """khp_debug_env_light_tables: the sampling table the context built on the device."""
+        e = self.env_light()
+        t = _env_tables(e["width"], e["height"])
+        N.check(self.lib, self.lib.khp_debug_env_light_tables(self.ptr, N.uptr(t["weight"]), N.uptr(t["row_cdf"]),
+                                                              _u64ptr(t["marginal"])), "khp_debug_env_light_tables")
+        return t
+
+    def debug_env_light(self, draws, dir_in) -> dict:
+        """khp_debug_env_light: the renderer's own sampler over draws (n, 2) and evaluation over dir_in (n, 3)
+        -> a dict of dir, pdf, radiance, valid (the samples) and e_radiance, e_pdf (the evaluations)."""
+        u = np.ascontiguousarray(draws, np.float32).reshape(-1, 2)
+        n = len(u)
+        d = np.ascontiguousarray(dir_in, np.float32).reshape(n, 3)
+        r = {"dir": np.empty((n, 3), np.float32), "pdf": np.empty(n, np.float32),
+             "radiance": np.empty((n, 3), np.float32), "valid": np.empty(n, np.int32),
+             "e_radiance": np.empty((n, 3), np.float32), "e_pdf": np.empty(n, np.float32)}
+        N.check(self.lib, self.lib.khp_debug_env_light(
+            self.ptr, n, N.fptr(u), N.fptr(d), N.fptr(r["dir"]), N.fptr(r["pdf"]), N.fptr(r["radiance"]),
+            r["valid"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), N.fptr(r["e_radiance"]), N.fptr(r["e_pdf"])),
+            "khp_debug_env_light")
+        return r
+
     def debug_camera_rays(self, width: int, pixels, samples, seed: int = 0x4B49524B):
         """khp_debug_camera_rays: the renderer's own camera rays (origins, directions) of the
         (pixel, sample) pairs, with the context's camera and lens; nothing of the context is touched."""
@@ -891,6 +941,65 @@ def hair_sample_host(materials, uvw, normal, wo, draws):
                                           N.fptr(r["out"]), N.fptr(r["pdf"]), N.fptr(r["f"]),
                                           r["valid"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
             "khp_hair_sample_host")
+    return r
+
+
+def _u64ptr(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+
+
+def _env_light_arg(rgb, scale=1.0, rotation=0.0, nee=True, select=0.5):
+    """A khp_env_light over a host map (height, width, 3), and the array it points into."""
+    a = np.ascontiguousarray(rgb, np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("rgb must have the shape (height, width, 3)")
+    prm = N.EnvLight(a.shape[1], a.shape[0], 0, int(bool(nee)), float(scale), float(rotation), float(select), 0,
+                     a.ctypes.data)
+    return prm, a
+
+
+def _env_tables(width, height):
+    return {"weight": np.empty((height, width), np.uint32), "row_cdf": np.empty((height, width + 1), np.uint32),
+            "marginal": np.empty(height + 1, np.uint64)}
+
+
+def env_light_tables_host(rgb, **params) -> dict:
+    """khp_env_light_tables_host: the sampling table of the map rgb (height, width, 3) as plain host loops
+    -> a dict of weight (H, W) uint32, row_cdf (H, W + 1) uint32 and marginal (H + 1) uint64."""
+    lib = N.load_library()
+    prm, a = _env_light_arg(rgb, **params)
+    t = _env_tables(a.shape[1], a.shape[0])
+    N.check(lib, lib.khp_env_light_tables_host(ctypes.byref(prm), N.uptr(t["weight"]), N.uptr(t["row_cdf"]),
+                                               _u64ptr(t["marginal"])), "khp_env_light_tables_host")
+    return t
+
+
+def env_light_sample_host(rgb, draws, **params) -> dict:
+    """khp_env_light_sample_host: one direction per item from the draws (n, 2), as a plain host loop over
+    the kernels' own function -> a dict of dir (n, 3), pdf (n), radiance (n, 3) and valid (n)."""
+    lib = N.load_library()
+    prm, _a = _env_light_arg(rgb, **params)
+    u = np.ascontiguousarray(draws, np.float32).reshape(-1, 2)
+    n = len(u)
+    r = {"dir": np.empty((n, 3), np.float32), "pdf": np.empty(n, np.float32),
+         "radiance": np.empty((n, 3), np.float32), "valid": np.empty(n, np.int32)}
+    N.check(lib, lib.khp_env_light_sample_host(ctypes.byref(prm), n, N.fptr(u), N.fptr(r["dir"]), N.fptr(r["pdf"]),
+                                               N.fptr(r["radiance"]),
+                                               r["valid"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+            "khp_env_light_sample_host")
+    return r
+
+
+def env_light_eval_host(rgb, dir, **params) -> dict:
+    """khp_env_light_eval_host: the map's radiance and the sampler's density in the directions dir (n, 3),
+    any length -> a dict of radiance (n, 3) and pdf (n)."""
+    lib = N.load_library()
+    prm, _a = _env_light_arg(rgb, **params)
+    d = np.ascontiguousarray(dir, np.float32).reshape(-1, 3)
+    n = len(d)
+    r = {"radiance": np.empty((n, 3), np.float32), "pdf": np.empty(n, np.float32)}
+    N.check(lib, lib.khp_env_light_eval_host(ctypes.byref(prm), n, N.fptr(d), N.fptr(r["radiance"]), N.fptr(r["pdf"])),
+            "khp_env_light_eval_host")
     return r
 
 

@@ -616,6 +616,30 @@ def checker(h: int, w: int, channels: int, cells: int = 4, seed: int = 7) -> np.
     return np.ascontiguousarray(cols[yy, xx])
 
 
+def sky_map(width: int, height: int, sun_dir=(0.3, 0.8, 0.5), sun_radiance=(4000.0, 3600.0, 3000.0),
+            sun_half_angle: float = 0.05, zenith=(0.25, 0.45, 1.0), horizon=(0.9, 0.95, 1.0),
+            ground=(0.12, 0.1, 0.08)) -> np.ndarray:
+    """A procedural latitude-longitude sky (height, width, 3) float32 for HipContext.set_env_light: row 0
+    is the -y pole, column i the azimuth (i + 0.5) 2 pi / width from +x towards +z.  Above the horizon the
+    colour goes from `horizon` to `zenith` with the elevation's sine, below it is `ground`; texels whose
+    centre lies within sun_half_angle (radians) of sun_dir hold sun_radiance, and the texel nearest to
+    sun_dir always does, so a map of any size has its sun."""
+    th = (np.arange(height) + 0.5) * (np.pi / height)
+    ph = (np.arange(width) + 0.5) * (2.0 * np.pi / width)
+    st, ct = np.sin(th)[:, None], np.cos(th)[:, None]
+    d = np.stack([st * np.cos(ph)[None, :], np.broadcast_to(-ct, (height, width)), st * np.sin(ph)[None, :]], -1)
+    up = np.clip(d[..., 1], 0.0, 1.0)[..., None]
+    sky = np.asarray(horizon, np.float64) * (1.0 - up) + np.asarray(zenith, np.float64) * up
+    img = np.where(d[..., 1:2] >= 0.0, sky, np.asarray(ground, np.float64))
+    s = np.asarray(sun_dir, np.float64)
+    s = s / np.linalg.norm(s)
+    c = d @ s
+    sun = c >= np.cos(sun_half_angle)
+    sun.reshape(-1)[np.argmax(c)] = True
+    img[sun] = np.asarray(sun_radiance, np.float64)
+    return np.ascontiguousarray(img, np.float32)
+
+
 def rotation(axis, angle_rad: float) -> np.ndarray:
     a = np.asarray(axis, np.float64)
     a /= np.linalg.norm(a)

@@ -937,6 +937,85 @@ khp_status khp_hair_sample_host(uint32_t n, const khp_material* materials, const
                                 const float* wo, const float* draws, float* out_dir, float* pdf, float* f,
                                 int32_t* valid);
 
+/* ---- an importance-sampled HDR environment light (additive) ---------
+ * KIRK's background is found only by rays that happen to escape, its texels end at 255,
+ * and no next-event ray is sent towards it.  khp_set_env_light gives the context a
+ * latitude-longitude map of float32 radiance and a sampling table built from it on the
+ * device; a context starts without one, and without one every frame, AOV plane and query
+ * is what it was, from the same kernel instances.  rgb is [height][width][3]; row 0 is
+ * the -y pole, column i spans the azimuths [i, i + 1) 2 pi / width + rotation measured from
+ * +x towards +z.  The definition is csrc/env_light.h, compiled for the host and for
+ * gfx950, the same bits; every float step is one float32 operation:
+ *   table    per texel p = ((0.2126 r + 0.7152 g) + 0.0722 b) * k_sinf((j + 0.5)(pi / H)), m
+ *            the largest p; weight = p > 0 ? max(1, (uint32)((p / m) * 2^19)) : 0;
+ *            row_cdf[j] the exclusive prefix of row j (W + 1 words, the row's sum last),
+ *            marginal the exclusive prefix of the row sums (H + 1 words, the total last).
+ *   sample   U = min((uint32)(u * 2^24), 2^24 - 1) for each of the two draws; X = floor(U0 *
+ *            total / 2^24) picks the row with marginal[j] <= X < marginal[j + 1], Y =
+ *            floor(U1 * rowsum / 2^24) the column likewise; inside the texel fy = min(((float)
+ *            (X - marginal[j]) + 0.5) / (float)rowsum, 1 - 2^-24), fx likewise with the
+ *            texel's weight; theta = (j + fy)(pi / H), phi = (i + fx)(2 pi / W) + rotation,
+ *            d = (sin theta cos phi, -cos theta, sin theta sin phi).  The sampler returns
+ *            eval(d), so the two agree bit for bit; valid is pdf > 0.
+ *   eval     n = normalize(d); theta = k_asinf(n.y) + pi/2, phi = k_atan2f(n.z, n.x) -
+ *            rotation; j = (int)(theta / (pi / H)), i = (int)((t - floor(t)) * W) with t =
+ *            phi / 2 pi, both clamped into the map; radiance = rgb[j][i] * scale (nearest
+ *            texel: the density's own piecewise-constant shape); pdf = (((float)weight /
+ *            (float)total) * (float)(W H)) / (2 pi^2 * sqrtf(n.x^2 + n.z^2)), 0 where the
+ *            root is 0.  A zero or NaN direction has radiance 0 and pdf 0.
+ * At a hit whose BSDF kind has a non-zero evaluateLight (Lambertian reflection and
+ * transmission, Marschner, kind 11) and with nee = 1, the hit's one shadow ray goes to the
+ * map with probability `select` (1 without lights), drawn by P_LIGHT_SEL, in a direction
+ * drawn by P_LIGHT_0 / P_LIGHT_1; otherwise KIRK's light choice is made from the rescaled
+ * draw and its term is divided by 1 - select.  An escaping ray adds the map's radiance
+ * iff nee = 0, or it is a camera ray, or the previous hit was of another kind (glass,
+ * mirror, glossy, d'Eon, transparent).  With the light on, env.color and env_map are not
+ * read for an escaping ray; the ambient term stays.
+ * khp_set_env_light copies the map and builds the table; it completes in-flight frames
+ * (they finish with the light they started with), drops render-ahead work and needs no
+ * rebuild; the framebuffer and the moments are not touched; khp_set_scene and
+ * khp_set_camera leave the light alone.  width = height = 0 turns the light off (rgb is
+ * not read).  KHP_EINVAL (checked before the context is touched; khp_last_error names the
+ * cause, the first bad texel included): a null argument, width outside 1..4096, height
+ * outside 1..2048, unknown flags, nee > 1, scale not finite and > 0, rotation not finite or
+ * beyond 8192 radians either way, select outside (0, 1], reserved != 0, a texel that is
+ * negative or not finite, a black map.  KHP_EUNSUPPORTED, in either order and changing
+ * nothing: the light with the light-path variant, or with hair lobes other than R.
+ * Frames with the light on have no CPU oracle. */
+#define KHP_ENV_LIGHT_DEVICE (1u << 0)   /* rgb is device memory of ctx's GPU */
+typedef struct {
+    uint32_t width, height;  /* offset 0, 4: 0 x 0: off (the default) */
+    uint32_t flags;          /* 8: KHP_ENV_LIGHT_* */
+    uint32_t nee;            /* 12: 1 (default): next-event rays towards the map; 0: escaping rays only */
+    float scale;             /* 16: radiance multiplier, finite, > 0 (default 1) */
+    float rotation;          /* 20: radians about +y, finite (default 0) */
+    float select;            /* 24: in (0, 1]: chance that a hit's one shadow ray goes to the map when
+                                the scene also has lights (default 0.5); ignored without lights */
+    uint32_t reserved;       /* 28: 0 */
+    const float* rgb;        /* 32: [height][width][3]; row 0 is the -y pole, like every image of this ABI */
+} khp_env_light;             /* 40 bytes */
+void       khp_env_light_defaults(khp_env_light* out);
+khp_status khp_set_env_light(khp_ctx* ctx, const khp_env_light* light);   /* copies the map, builds the table */
+khp_status khp_get_env_light(khp_ctx* ctx, khp_env_light* out);           /* rgb comes back NULL */
+/* The definition as plain host loops (no device, no context; a host map only).  Tables:
+ * weight [H][W], row_cdf [H][W + 1], marginal [H + 1].  Sample: draws [n][2] give dir
+ * [n][3], pdf [n], radiance [n][3], valid [n].  Eval: dir [n][3] (any length) gives
+ * radiance [n][3] and pdf [n].  KHP_EINVAL: what khp_set_env_light refuses, a device map, a
+ * null array, n outside [1, 2^20]. */
+khp_status khp_env_light_tables_host(const khp_env_light* light, uint32_t* weight, uint32_t* row_cdf,
+                                     uint64_t* marginal);
+khp_status khp_env_light_sample_host(const khp_env_light* light, uint32_t n, const float* draws, float* dir,
+                                     float* pdf, float* radiance, int32_t* valid);
+khp_status khp_env_light_eval_host(const khp_env_light* light, uint32_t n, const float* dir, float* radiance,
+                                   float* pdf);
+/* Test hooks in the style of the khp_debug_* queries: the tables the context built on the
+ * device, and the device functions the renderer calls, one thread per item (the sampler
+ * over draws, the evaluation over dir_in), on scratch of their own.  KHP_ENOTREADY
+ * without a light. */
+khp_status khp_debug_env_light_tables(khp_ctx* ctx, uint32_t* weight, uint32_t* row_cdf, uint64_t* marginal);
+khp_status khp_debug_env_light(khp_ctx* ctx, uint32_t n, const float* draws, const float* dir_in, float* s_dir,
+                               float* s_pdf, float* s_radiance, int32_t* s_valid, float* e_radiance, float* e_pdf);
+
 /* Completes every frame enqueued with KHP_RENDER_ASYNC (ABI 5).  A progressive
  * caller (KIRK's PathTracer::render loop) enqueues its passes and syncs before
  * reading the texture; passes accumulate in call order.  Any synchronous call
