@@ -26,7 +26,7 @@ from .native import (AOV_CHANNELS, DENOISE_DEMODULATE, DENOISE_DEVICE, HAIR_LOBE
                      DenoiseNoise, DenoiseParams, ReprojectFrame, ReprojectOut, ReprojectParams)
 from .pathtracer import (BVH, BsdfFactory, HipContext, PathTracer, ShaderFactory, TemporalAccumulator,  # noqa: E402
                          adaptive_select_host, camera_rays_host, comm_unique_id, denoise_host, denoise_var_host,
-                         env_light_eval_host, env_light_sample_host, env_light_tables_host, hair_eval_host,
+                         env_light_eval_host, env_light_sample_host, env_light_tables_host, hair_eval_host, kmath_host,
                          hair_sample_host, lens_from_kirk, moments_fold_host, moments_variance, reproject_host)
 from .scenes import SceneData, build_config  # noqa: E402
 
@@ -37,4 +37,4 @@ __all__ = ["set_hw_queues", "native", "BVH", "BsdfFactory", "HipContext", "PathT
            "NOISE_PLANE", "NOISE_MOMENTS", "NOISE_CONTEXT", "denoise_var_host", "ReprojectParams", "ReprojectFrame",
            "ReprojectOut", "REPROJECT_DEVICE", "REPROJECT_MATCH_OBJECT", "reproject_host", "TemporalAccumulator",
            "LENS_FOCUS_KIRK", "LENS_FOCUS_PLANE", "lens_from_kirk", "camera_rays_host", "hair_eval_host", "hair_sample_host",
-           "env_light_tables_host", "env_light_sample_host", "env_light_eval_host"]
+           "env_light_tables_host", "env_light_sample_host", "env_light_eval_host", "kmath_host"]

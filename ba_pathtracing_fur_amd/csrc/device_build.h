@@ -107,6 +107,10 @@ std::string device_gen_hairball_tris(uint32_t n, uint32_t verts, const float cen
                                      uint32_t seed, uint32_t res, float* d_v, float* d_n, float* d_frame,
                                      hipStream_t st);
 
+// khp_debug_kmath (flatten.hip): op of kmath_ops.h over n items of host words, one per
+// thread.  Checks op, n and the pointers itself; errors starting "EINVAL:" are input errors.
+std::string device_kmath(uint32_t op, uint32_t n, const uint64_t* in, uint64_t* out, hipStream_t st);
+
 // BVH::addBaseDataStructure on the device from o.centroid / o.bounds: the host
 // builder's tree (build_bvh), node for node.  Sets hs.depth / hs.max_leaf.
 std::string device_build_bvh(HostScene& hs, const DeviceObjects& o, hipStream_t st, DeviceTree& t,

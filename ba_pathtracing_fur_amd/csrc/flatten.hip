@@ -10,6 +10,7 @@
 #include <string>
 
 #include "device_build.h"
+#include "kmath_ops.h"
 #include "objects.h"
 
 namespace khp {
@@ -197,7 +198,36 @@ __global__ void k_check_hair_tris(const uint32_t* tm, uint32_t nt, const uint8_t
     if (m < n_mat && hair[m]) atomicOr(err, 128u);
 }
 
+// khp_debug_kmath: one item per thread through kmath_ops.h's table, the gfx950 compile of
+// what khp_kmath_host loops over.  It lives here and not beside the other queries so that
+// no kernel of the render translation unit is compiled next to it.
+__global__ void __launch_bounds__(256) k_dbg_kmath(uint32_t op, uint32_t n, const uint64_t* __restrict__ in,
+                                                   uint64_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint64_t w[KMATH_WORDS], o[KMATH_WORDS];
+    for (int k = 0; k < KMATH_WORDS; ++k) w[k] = in[KMATH_WORDS * (size_t)i + k];
+    kmath_apply(op, w, o);
+    for (int k = 0; k < KMATH_WORDS; ++k) out[KMATH_WORDS * (size_t)i + k] = o[k];
+}
+
 }  // namespace fl
+
+std::string device_kmath(uint32_t op, uint32_t n, const uint64_t* in, uint64_t* out, hipStream_t st) {
+    using namespace fl;
+    if (const char* why = kmath_args_error(op, n, in, out)) return std::string("EINVAL:khp_debug_kmath: ") + why;
+    const size_t bytes = sizeof(uint64_t) * KMATH_WORDS * (size_t)n;
+    DevMem din, dout;
+    FLCHK(din.ensure(bytes));
+    FLCHK(dout.ensure(bytes));
+    FLCHK(hipMemcpyAsync(din.p, in, bytes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_dbg_kmath, dim3(blocks(n, 256)), dim3(256), 0, st, op, n, din.as<uint64_t>(),
+                       dout.as<uint64_t>());
+    FLCHK(hipGetLastError());
+    FLCHK(hipMemcpyAsync(out, dout.p, bytes, hipMemcpyDeviceToHost, st));
+    FLCHK(hipStreamSynchronize(st));
+    return std::string();
+}
 
 std::string device_flatten(const khp_scene* s, bool device_ptrs, uint32_t n_materials, bool textured,
                            const std::vector<float>& models, DeviceObjects& o, hipStream_t st, double* kernel_ms) {

@@ -72,6 +72,21 @@ constexpr float DP1 = 0.78515625f;
 constexpr float DP2 = 2.4187564849853515625e-4f;
 constexpr float DP3 = 3.77489497744594108e-8f;
 constexpr float FOPI = 1.27323954473516f;
+// DP3 is pi/4 - DP1 - DP2 rounded to float32, and y * DP3 is rounded again: about y * 2.3e-15 of
+// absolute error in the reduced argument, which is all of the result next to a zero of the function
+// (13.8 ulp at k_sinf(3 pi), k_cosf(3 pi / 2)).  A reduced argument below 2^-20 -- where that error,
+// at y <= 16, would pass 0.6 ulp of it -- is therefore taken again with DP3 in two parts: DP3A has 11
+// significant bits, so y * DP3A is exact for y < 2^13, and y * DP3B's rounding is below 1e-18.
+// Every other argument keeps the three-constant sequence and its bits.
+constexpr float DP3A = 0x1.444p-25f;      // 3.7747668102383614e-08
+constexpr float DP3B = 0x1.68c234p-40f;   // 1.2816720341285448e-12 = pi/4 - DP1 - DP2 - DP3A
+constexpr float REDUCE_TINY = 0x1p-20f;
+KHD float k_reduce(float x, float y) {
+    const float r2 = (x - y * DP1) - y * DP2;
+    const float r = r2 - y * DP3;
+    if (k_fabs(r) < REDUCE_TINY) return (r2 - y * DP3A) - y * DP3B;
+    return r;
+}
 
 KHD float k_sinf(float x) {
     if (k_isnan(x)) return x;
@@ -82,7 +97,7 @@ KHD float k_sinf(float x) {
     if (j & 1) { j += 1; y += 1.0f; }
     j &= 7;
     if (j > 3) { neg = !neg; j -= 4; }
-    x = ((x - y * DP1) - y * DP2) - y * DP3;
+    x = k_reduce(x, y);
     float z = x * x;
     y = (j == 1 || j == 2) ? k_cos_poly(z) : k_sin_poly(z, x);
     return neg ? -y : y;
@@ -98,7 +113,7 @@ KHD float k_cosf(float x) {
     j &= 7;
     if (j > 3) { j -= 4; neg = !neg; }
     if (j > 1) neg = !neg;
-    x = ((x - y * DP1) - y * DP2) - y * DP3;
+    x = k_reduce(x, y);
     float z = x * x;
     y = (j == 1 || j == 2) ? k_sin_poly(z, x) : k_cos_poly(z);
     return neg ? -y : y;

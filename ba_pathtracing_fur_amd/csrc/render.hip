@@ -3472,6 +3472,19 @@ extern "C" khp_status khp_gen_fur_device(khp_ctx* c, const khp_fur_params* p, ui
     return KHP_OK;
 }
 
+// kmath.h on the device, op by op (kmath_ops.h); the kernel and its argument checks are flatten.hip's.
+extern "C" khp_status khp_debug_kmath(khp_ctx* c, uint32_t op, uint32_t n, const uint64_t* in, uint64_t* out) {
+    if (!c) return fail(KHP_EINVAL, "khp_debug_kmath: ctx is null");
+    KHPCHK(drain(c));  // complete asynchronous frames first
+    HIPCHK(hipSetDevice(c->device));
+    std::string err = device_kmath(op, n, in, out, c->stream);
+    if (!err.empty()) {
+        if (err.rfind("EINVAL:", 0) == 0) return fail(KHP_EINVAL, err.substr(7));
+        return fail(KHP_EDEVICE, err);
+    }
+    return KHP_OK;
+}
+
 extern "C" khp_status khp_device_alloc(khp_ctx* c, size_t bytes, void** out) {
     if (!c || !out) return fail(KHP_EINVAL, "null argument");
     HIPCHK(hipSetDevice(c->device));

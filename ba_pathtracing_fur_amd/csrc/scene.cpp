@@ -17,7 +17,7 @@
 
 namespace khp {
 
-
+constexpr float KMATH_MAX_ANGLE = 8192.0f;   // a scene's angles beyond this are refused (k_sinf's range, as ENV_ROTATION_MAX)
 
 // Light ctors + QuadLight::calcParams + Light::transform(identity)
 // (Common/Light.h ctors, Light.cpp:112-118, 216-220, 263-276).
@@ -155,9 +155,17 @@ std::string flatten_scene(const khp_scene* s, HostScene& hs, bool objects) {
         if (m.shader < 0 || m.shader >= KHP_SHADER_COUNT) return "unknown shader kind";
         if (m.bsdf == KHP_BSDF_CHIANG_HAIR)
             if (const char* why = hair_material_error(m)) return "material " + std::to_string(i) + ": " + why;
+        // k_sinf / k_cosf count octants in an int: every angle a scene can set stays inside their
+        // domain, as khp_set_env_light's rotation does.  sample_angle's cone:
+        if ((m.bsdf == KHP_BSDF_GLOSSY || m.bsdf == KHP_BSDF_MILK_GLASS) &&
+            fabsf((180.0f - (1.0f - m.roughness) * 180.0f) * DEG2RAD) > KMATH_MAX_ANGLE)
+            return "material " + std::to_string(i) + ": roughness puts the lobe's cone angle beyond 8192 radians";
     }
-    for (uint32_t i = 0; i < s->n_lights; ++i)
+    for (uint32_t i = 0; i < s->n_lights; ++i) {
         if (s->lights[i].kind < 0 || s->lights[i].kind > KHP_LIGHT_SUN) return "unknown light kind";
+        if (s->lights[i].kind == KHP_LIGHT_SPOT && fabsf(s->lights[i].outer_angle * DEG2RAD) > KMATH_MAX_ANGLE)
+            return "light " + std::to_string(i) + ": outer_angle is beyond 8192 radians";
+    }
     hs = HostScene();
     hs.n_tris = s->n_tris;
     hs.n_cones = s->n_cones;

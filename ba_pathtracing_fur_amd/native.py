@@ -373,7 +373,15 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_get_lens", "khp_camera_rays_host", "khp_debug_camera_rays", "khp_hair_material",
             "khp_hair_eval_host", "khp_hair_sample_host", "khp_env_light_defaults", "khp_set_env_light",
             "khp_get_env_light", "khp_env_light_tables_host", "khp_env_light_sample_host", "khp_env_light_eval_host",
-            "khp_debug_env_light_tables", "khp_debug_env_light"]
+            "khp_debug_env_light_tables", "khp_debug_env_light", "khp_kmath_host", "khp_debug_kmath"]
+
+# khp_kmath_op (include/kirk_hip.h): the ops of khp_kmath_host / khp_debug_kmath, in enum order
+KMATH_OPS = ("mul", "add", "div", "sqrt", "rsqrt", "muladd", "floor", "f2i", "f2u", "i2f", "u2f", "u642f", "d2i2d",
+             "dmul", "dadd", "ddiv", "umulhi", "ldexpf", "sinf", "cosf", "atanf", "atan2f", "asinf", "acosf", "expf",
+             "sinhf", "hypotf", "logf_d", "powf_d", "j0", "log_d", "exp_d", "pow_d", "lowbias32", "path_key",
+             "draw_u32", "draw_u01", "dot", "cross", "normalize", "reflect", "refract", "rotate_rowvec", "angle",
+             "faceforward", "gmin", "gmax", "gclamp")
+KMATH_OP = {name: i for i, name in enumerate(KMATH_OPS)}
 
 # the include/kirk_hip.h this module mirrors (load_library refuses another)
 ABI_VERSION = 17
@@ -521,6 +529,8 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_debug_env_light_tables": (c_int, [c_void_p, P(c_uint32), P(c_uint32), P(ctypes.c_uint64)]),
         "khp_debug_env_light": (c_int, [c_void_p, c_uint32, P(c_float), P(c_float), P(c_float), P(c_float), P(c_float),
                                         P(c_int32), P(c_float), P(c_float)]),
+        "khp_kmath_host": (c_int, [c_uint32, c_uint32, P(ctypes.c_uint64), P(ctypes.c_uint64)]),
+        "khp_debug_kmath": (c_int, [c_void_p, c_uint32, c_uint32, P(ctypes.c_uint64), P(ctypes.c_uint64)]),
         "khp_debug_hair_sample": (c_int, [c_void_p, c_uint32, c_uint32, P(c_int32), P(c_int32), P(c_float), P(c_float),
                                           P(c_float), P(c_float), P(c_int32), P(c_float), P(c_float), P(c_float),
                                           P(c_float), P(c_int32), P(c_int32)]),

@@ -298,6 +298,14 @@ class HipContext:
             "khp_debug_env_light")
         return r
 
+    def debug_kmath(self, op, items) -> np.ndarray:
+        """khp_debug_kmath: one op of csrc/kmath_ops.h (a name of native.KMATH_OPS or its number) over
+        items (n, 3) of raw uint64 words, one thread per item on the device; returns the (n, 3) output words."""
+        w, o = _kmath_items(items)
+        N.check(self.lib, self.lib.khp_debug_kmath(self.ptr, _kmath_op(op), len(w), _u64ptr(w), _u64ptr(o)),
+                "khp_debug_kmath")
+        return o
+
     def debug_camera_rays(self, width: int, pixels, samples, seed: int = 0x4B49524B):
         """khp_debug_camera_rays: the renderer's own camera rays (origins, directions) of the
         (pixel, sample) pairs, with the context's camera and lens; nothing of the context is touched."""
@@ -946,6 +954,27 @@ def hair_sample_host(materials, uvw, normal, wo, draws):
 
 def _u64ptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+
+
+def _kmath_op(op) -> int:
+    return N.KMATH_OP[op] if isinstance(op, str) else int(op)
+
+
+def _kmath_items(items):
+    w = np.ascontiguousarray(items, np.uint64)
+    if w.ndim != 2 or w.shape[1] != 3:
+        raise ValueError("items must have the shape (n, 3)")
+    return w, np.empty_like(w)
+
+
+def kmath_host(op, items) -> np.ndarray:
+    """khp_kmath_host: one op of csrc/kmath_ops.h (a name of native.KMATH_OPS or its number) over items
+    (n, 3) of raw uint64 words, as the host compiler builds kmath.h (no device, no context); returns the
+    (n, 3) output words.  Nothing is converted: a float32 argument is the low half of its word."""
+    w, o = _kmath_items(items)
+    lib = N.load_library()
+    N.check(lib, lib.khp_kmath_host(_kmath_op(op), len(w), _u64ptr(w), _u64ptr(o)), "khp_kmath_host")
+    return o
 
 
 def _env_light_arg(rgb, scale=1.0, rotation=0.0, nee=True, select=0.5):

@@ -1016,6 +1016,67 @@ khp_status khp_debug_env_light_tables(khp_ctx* ctx, uint32_t* weight, uint32_t* 
 khp_status khp_debug_env_light(khp_ctx* ctx, uint32_t n, const float* draws, const float* dir_in, float* s_dir,
                                float* s_pdf, float* s_radiance, int32_t* s_valid, float* e_radiance, float* e_pdf);
 
+/* ---- kmath itself, op by op, on the host and on the device ------------
+ * The numeric definitions of csrc/kmath.h are compiled twice, by the host compiler and for
+ * gfx950, and every parity claim of this library rests on the two giving the same bits.
+ * These two entries apply one op of csrc/kmath_ops.h to n items so that a test can hold
+ * each compile to a truth and the two to one another.  Item i reads the three 64-bit words
+ * in[3 i .. 3 i + 2] and writes the three words out[3 i .. 3 i + 2] (unused outputs are 0).
+ * Nothing is converted at the boundary: subnormals, NaN payloads and signed zeros arrive as
+ * given.  A scalar float32 / uint32 / int32 argument k is the low half of word k, a float64
+ * / uint64 / int64 argument is word k; a float32 result is the low half of out word 0 (the
+ * high half 0).  The algebra ops read six floats f0..f5 = the low and high halves of words
+ * 0, 1, 2 in that order, and write one float per output word:
+ *   DOT, CROSS, REFLECT, ANGLE   (a, b) = (f0 f1 f2), (f3 f4 f5) in the function's order
+ *   NORMALIZE                    (f0 f1 f2)
+ *   REFRACT                      I = (f0 f1 f2), N = (f3 f4 f5), eta = f5
+ *   ROTATE_ROWVEC                d = (f0 f1 f2), angle = f3, axis = (f4 f5 f2)
+ *   FACEFORWARD                  N = Nref = (f0 f1 f2), I = (f3 f4 f5)
+ *   GMIN, GMAX (f0, f2), GCLAMP (f0, f2, f4): scalars, one per word
+ * (seven- and nine-float argument lists share a float so that an item stays three words).
+ * khp_kmath_host needs no device and no context.  khp_debug_kmath runs one item per thread
+ * in the manner of the khp_debug_* queries, on scratch of its own; it needs no scene, and
+ * leaves the framebuffer, the moments and khp_stats alone.  KHP_EINVAL, before anything is
+ * launched: a null argument, an op outside [0, KHP_KMATH_OP_COUNT), n outside [1, 2^20]. */
+typedef enum {
+    /* IEEE primitives as kmath writes them */
+    KHP_KMATH_MUL = 0,        /* a * b */
+    KHP_KMATH_ADD = 1,        /* a + b */
+    KHP_KMATH_DIV = 2,        /* a / b */
+    KHP_KMATH_SQRT = 3,       /* sqrtf(a) */
+    KHP_KMATH_RSQRT = 4,      /* 1.0f / sqrtf(a) */
+    KHP_KMATH_MULADD = 5,     /* t = a * b; t + c: two roundings */
+    KHP_KMATH_FLOOR = 6,      /* floorf(a) */
+    KHP_KMATH_F2I = 7,        /* (int)a, in-range a */
+    KHP_KMATH_F2U = 8,        /* (uint32_t)a, in-range a */
+    KHP_KMATH_I2F = 9,        /* (float)(int) */
+    KHP_KMATH_U2F = 10,       /* (float)(uint32_t) */
+    KHP_KMATH_U642F = 11,     /* (float)(uint64_t) */
+    KHP_KMATH_D2I2D = 12,     /* (double)(int64_t)d, in-range d */
+    KHP_KMATH_DMUL = 13, KHP_KMATH_DADD = 14, KHP_KMATH_DDIV = 15,   /* double a * b, a + b, a / b */
+    KHP_KMATH_UMULHI = 16,    /* the high 64 bits of a 64 x 64 product (env_light.h) */
+    /* float functions */
+    KHP_KMATH_LDEXPF = 17,    /* k_ldexpf(a, (int32)b) */
+    KHP_KMATH_SINF = 18, KHP_KMATH_COSF = 19, KHP_KMATH_ATANF = 20,
+    KHP_KMATH_ATAN2F = 21,    /* k_atan2f(y = a, x = b) */
+    KHP_KMATH_ASINF = 22, KHP_KMATH_ACOSF = 23, KHP_KMATH_EXPF = 24, KHP_KMATH_SINHF = 25,
+    KHP_KMATH_HYPOTF = 26, KHP_KMATH_LOGF_D = 27, KHP_KMATH_POWF_D = 28,
+    /* double functions */
+    KHP_KMATH_J0 = 29, KHP_KMATH_LOG_D = 30, KHP_KMATH_EXP_D = 31, KHP_KMATH_POW_D = 32,
+    /* integers */
+    KHP_KMATH_LOWBIAS32 = 33,
+    KHP_KMATH_PATH_KEY = 34,  /* path_key(seed = a, pixel = b, sample = c) */
+    KHP_KMATH_DRAW_U32 = 35,  /* draw_u32(key = a, dim = b) */
+    KHP_KMATH_DRAW_U01 = 36,  /* draw_u01(key = a, dim = b) */
+    /* algebra */
+    KHP_KMATH_DOT = 37, KHP_KMATH_CROSS = 38, KHP_KMATH_NORMALIZE = 39, KHP_KMATH_REFLECT = 40,
+    KHP_KMATH_REFRACT = 41, KHP_KMATH_ROTATE_ROWVEC = 42, KHP_KMATH_ANGLE = 43, KHP_KMATH_FACEFORWARD = 44,
+    KHP_KMATH_GMIN = 45, KHP_KMATH_GMAX = 46, KHP_KMATH_GCLAMP = 47,
+    KHP_KMATH_OP_COUNT = 48
+} khp_kmath_op;
+khp_status khp_kmath_host(uint32_t op, uint32_t n, const uint64_t* in, uint64_t* out);
+khp_status khp_debug_kmath(khp_ctx* ctx, uint32_t op, uint32_t n, const uint64_t* in, uint64_t* out);
+
 /* Completes every frame enqueued with KHP_RENDER_ASYNC (ABI 5).  A progressive
  * caller (KIRK's PathTracer::render loop) enqueues its passes and syncs before
  * reading the texture; passes accumulate in call order.  Any synchronous call

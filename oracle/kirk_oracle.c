@@ -64,7 +64,16 @@ static float k_cos_poly(float z) {
 #define K_DP1 0.78515625f
 #define K_DP2 2.4187564849853515625e-4f
 #define K_DP3 3.77489497744594108e-8f
+/* a reduced argument below 2^-20 is taken again with DP3 in two parts (kmath.h: k_reduce) */
+#define K_DP3A 0x1.444p-25f
+#define K_DP3B 0x1.68c234p-40f
 #define K_FOPI 1.27323954473516f
+static float k_reduce(float x, float y) {
+    const float r2 = (x - y * K_DP1) - y * K_DP2;
+    const float r = r2 - y * K_DP3;
+    if (fabsf(r) < 0x1p-20f) return (r2 - y * K_DP3A) - y * K_DP3B;
+    return r;
+}
 
 float ko_sinf(float x) {
     float sign = 1.0f;
@@ -75,7 +84,7 @@ float ko_sinf(float x) {
     if (j & 1) { j += 1; y += 1.0f; }
     j &= 7;
     if (j > 3) { sign = -sign; j -= 4; }
-    x = ((x - y * K_DP1) - y * K_DP2) - y * K_DP3;
+    x = k_reduce(x, y);
     float z = x * x;
     y = (j == 1 || j == 2) ? k_cos_poly(z) : k_sin_poly(z, x);
     return sign < 0.0f ? -y : y;
@@ -91,7 +100,7 @@ float ko_cosf(float x) {
     j &= 7;
     if (j > 3) { j -= 4; sign = -sign; }
     if (j > 1) sign = -sign;
-    x = ((x - y * K_DP1) - y * K_DP2) - y * K_DP3;
+    x = k_reduce(x, y);
     float z = x * x;
     y = (j == 1 || j == 2) ? k_sin_poly(z, x) : k_cos_poly(z);
     return sign < 0.0f ? -y : y;
@@ -207,6 +216,38 @@ static uint32_t draw_u32(uint32_t key, uint32_t dim) { return lowbias32(key ^ (d
 static float draw_u01(uint32_t key, uint32_t dim) { return (float)(draw_u32(key, dim) >> 8) * (1.0f / 16777216.0f); }
 uint32_t ko_rand_u32(uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t dim) {
     return draw_u32(path_key(seed, pixel, sample), dim);
+}
+
+/* The single functions above over a batch of raw words (three 64-bit words per item in,
+ * one out), so that a test can compare millions of items: a float argument is the low
+ * half of its word.  fn: 0 sinf, 1 cosf, 2 atan2f(y, x), 3 acosf, 4 asinf, 5 expf, 6 sinhf,
+ * 7 j0, 8 log_d, 9 exp_d, 10 pow_d(x, y), 11 rand_u32(seed, pixel, sample | dim << 32). */
+static float w_f(uint64_t w) { union { uint32_t u; float f; } c; c.u = (uint32_t)w; return c.f; }
+static uint64_t f_w(float f) { union { uint32_t u; float f; } c; c.f = f; return c.u; }
+static double w_d(uint64_t w) { union { uint64_t u; double d; } c; c.u = w; return c.d; }
+static uint64_t d_w(double d) { union { uint64_t u; double d; } c; c.d = d; return c.u; }
+int ko_math_n(uint32_t fn, uint32_t n, const uint64_t* in, uint64_t* out) {
+    if (fn > 11u || !in || !out) return -1;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t* w = in + 3 * (size_t)i;
+        uint64_t r = 0;
+        switch (fn) {
+        case 0: r = f_w(ko_sinf(w_f(w[0]))); break;
+        case 1: r = f_w(ko_cosf(w_f(w[0]))); break;
+        case 2: r = f_w(ko_atan2f(w_f(w[0]), w_f(w[1]))); break;
+        case 3: r = f_w(ko_acosf(w_f(w[0]))); break;
+        case 4: r = f_w(ko_asinf(w_f(w[0]))); break;
+        case 5: r = f_w(ko_expf(w_f(w[0]))); break;
+        case 6: r = f_w(ko_sinhf(w_f(w[0]))); break;
+        case 7: r = d_w(ko_j0(w_d(w[0]))); break;
+        case 8: r = d_w(ko_log_d(w_d(w[0]))); break;
+        case 9: r = d_w(ko_exp_d(w_d(w[0]))); break;
+        case 10: r = d_w(ko_pow_d(w_d(w[0]), w_d(w[1]))); break;
+        default: r = ko_rand_u32((uint32_t)w[0], (uint32_t)w[1], (uint32_t)w[2], (uint32_t)(w[2] >> 32)); break;
+        }
+        out[i] = r;
+    }
+    return 0;
 }
 /* draw purposes, dim = bounce*16 + purpose */
 enum { P_CAM_X = 0, P_CAM_Y = 1, P_BSDF_0 = 2, P_BSDF_1 = 3, P_LIGHT_SEL = 4, P_LIGHT_0 = 5, P_LIGHT_1 = 6,

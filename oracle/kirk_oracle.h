@@ -86,6 +86,8 @@ float ko_expf(float x);
 float ko_sinhf(float x);
 double ko_j0(double x);
 uint32_t ko_rand_u32(uint32_t seed, uint32_t pixel, uint32_t sample, uint32_t dim);
+/* The same functions and ko_log_d / ko_exp_d / ko_pow_d over n items of raw words (kirk_oracle.c). */
+int ko_math_n(uint32_t fn, uint32_t n, const uint64_t* in, uint64_t* out);
 
 /* One BSDF::sample call (Bsdf.cpp:179-184) on a synthetic hit.
  * hit_obj: object id whose U/V/W frame (cones) is used; mat: material.

@@ -70,6 +70,7 @@ def load():
         "ko_exp_d": (c_double, [c_double]),
         "ko_pow_d": (c_double, [c_double, c_double]),
         "ko_rand_u32": (c_uint32, [c_uint32, c_uint32, c_uint32, c_uint32]),
+        "ko_math_n": (c_int, [c_uint32, c_uint32, P(c_uint64), P(c_uint64)]),
         "ko_bsdf_sample": (c_int, [c_void_p, c_int, c_void_p, P(c_float), P(c_float), P(c_float), P(c_float), c_int,
                                    P(c_float), P(c_float), P(c_float)]),
         "ko_bsdf_sample_n": (c_int, [c_void_p, c_uint32, P(c_int32), P(c_int32), P(c_float), P(c_float), P(c_float),

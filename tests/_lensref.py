@@ -22,6 +22,7 @@ PI_2 = np.float32(np.pi / 2)     # 0x3FC90FDB
 # kmath.h: Cephes sinf / cosf
 FOPI = F32(1.27323954473516)
 DP1, DP2, DP3 = F32(0.78515625), F32(2.4187564849853515625e-4), F32(3.77489497744594108e-8)
+DP3A, DP3B = F32(float.fromhex("0x1.444p-25")), F32(float.fromhex("0x1.68c234p-40"))
 S0, S1, S2 = F32(-1.9515295891E-4), F32(8.3321608736E-3), F32(1.6666654611E-1)
 C0, C1, C2 = F32(2.443315711809948E-005), F32(1.388731625493765E-003), F32(4.166664568298827E-002)
 
@@ -44,7 +45,9 @@ def _reduce(x):
     j = np.where(odd, j + 1, j)
     y = np.where(odd, y + F32(1.0), y).astype(F32)
     j = j & 7
-    r = ((x - y * DP1) - y * DP2) - y * DP3
+    r2 = (x - y * DP1) - y * DP2
+    r = r2 - y * DP3
+    r = np.where(np.abs(r) < F32(2.0 ** -20), (r2 - y * DP3A) - y * DP3B, r).astype(F32)   # k_reduce's second take
     return j, r, r * r
 
 

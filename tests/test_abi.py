@@ -1,7 +1,7 @@
 """The C-ABI drop-in boundary (include/kirk_hip.h): library loads, exports what the
 header declares, registries mirror KIRK's factories, errors are loud.  CPU only (khp_create is
 checked to *fail* without a GPU), except the bad-argument cases of the ABI 15
-and ABI 17 batch queries, which need a context (`gpu`).
+and ABI 17 batch queries and of khp_debug_kmath, which need a context (`gpu`).
 """
 import ctypes
 import os
@@ -363,3 +363,44 @@ def test_bdpt_queries_refuse_bad_arguments(hip_ctx):
         assert _bdpt_query_calls(4)[2][1](lib, c) == N.KHP_EINVAL and "no lights" in err()
     finally:
         hip_ctx.set_bdpt(**old)
+
+
+# ---- kmath op by op: khp_kmath_host and khp_debug_kmath (no ABI change: new entries only) --------
+def _kmath_call(entry, ctx, op=0, n=4, null=None):
+    """entry(lib) over n items (arrays of 4: a larger n is to be refused before anything is read)."""
+    P = ctypes.POINTER(ctypes.c_uint64)
+    w, o = np.zeros((4, 3), np.uint64), np.full((4, 3), 7, np.uint64)
+    a = ctypes.cast(None, P) if null == "in" else w.ctypes.data_as(P)
+    b = ctypes.cast(None, P) if null == "out" else o.ctypes.data_as(P)
+    lib = N.load_library()
+    rc = lib.khp_kmath_host(op, n, a, b) if entry == "host" else lib.khp_debug_kmath(ctx, op, n, a, b)
+    return rc, o
+
+
+def _kmath_bad_arguments(entry, ctx):
+    lib = N.load_library()
+    err = lambda: lib.khp_last_error().decode()
+    rc, o = _kmath_call(entry, ctx)
+    assert rc == N.KHP_OK and not o.any(), err()                        # 0 * 0 = +0 in every item
+    for op in (N.KMATH_OP["gclamp"] + 1, 1 << 16, 0xFFFFFFFF):
+        rc, o = _kmath_call(entry, ctx, op=op)
+        assert rc == N.KHP_EINVAL and "unknown op" in err() and (o == 7).all(), op
+    for n in (0, (1 << 20) + 1, 0xFFFFFFFF):
+        rc, o = _kmath_call(entry, ctx, n=n)
+        assert rc == N.KHP_EINVAL and "n must be" in err() and (o == 7).all(), n
+    for arg in ("in", "out"):
+        rc, o = _kmath_call(entry, ctx, null=arg)
+        assert rc == N.KHP_EINVAL and "null" in err() and (o == 7).all(), arg
+
+
+def test_kmath_host_refuses_bad_arguments_and_debug_kmath_needs_a_context():
+    _kmath_bad_arguments("host", None)
+    rc, o = _kmath_call("device", None)
+    assert rc == N.KHP_EINVAL and b"null" in N.load_library().khp_last_error() and (o == 7).all()
+    assert len(N.KMATH_OPS) == N.KMATH_OP["gclamp"] + 1 == 48
+
+
+@pytest.mark.gpu
+def test_debug_kmath_refuses_bad_arguments(hip_ctx):
+    """Every argument of khp_debug_kmath is checked on the host: an unknown op, a bad n or a null array launches nothing."""
+    _kmath_bad_arguments("device", hip_ctx.ptr)

@@ -4,6 +4,12 @@ KIRK calls libm / MSVC CRT (sin, cos, atan2, acos, exp, sinh, _j0); both the
 oracle and the kernels use the kmath restatements instead, so they must be
 within a few float ulps of the true functions over the ranges the hot path
 uses.  Parity between oracle and product is then bit-exact by construction.
+
+These are the oracle's restatement on a few thousand points.  The product's own compiles of
+csrc/kmath.h are held to a truth, to this restatement and to one another on about a million
+items per function in tests/test_kmath_truth.py (the host compile, through khp_kmath_host)
+and tests/test_gpu_kmath.py (the gfx950 compile, through khp_debug_kmath); the numpy
+restatement and the inputs they share are tests/_kmathref.py.
 """
 import numpy as np
 import pytest
