@@ -28,6 +28,7 @@ from .pathtracer import (BVH, BsdfFactory, HipContext, PathTracer, ShaderFactory
                          adaptive_select_host, camera_rays_host, comm_unique_id, denoise_host, denoise_var_host,
                          env_light_eval_host, env_light_sample_host, env_light_tables_host, hair_eval_host, kmath_host,
                          hair_sample_host, lens_from_kirk, moments_fold_host, moments_variance, reproject_host)
+from .native import refit_host  # noqa: E402
 from .scenes import SceneData, build_config  # noqa: E402
 
 __all__ = ["set_hw_queues", "native", "BVH", "BsdfFactory", "HipContext", "PathTracer", "ShaderFactory", "SceneData",
@@ -37,4 +38,4 @@ __all__ = ["set_hw_queues", "native", "BVH", "BsdfFactory", "HipContext", "PathT
            "NOISE_PLANE", "NOISE_MOMENTS", "NOISE_CONTEXT", "denoise_var_host", "ReprojectParams", "ReprojectFrame",
            "ReprojectOut", "REPROJECT_DEVICE", "REPROJECT_MATCH_OBJECT", "reproject_host", "TemporalAccumulator",
            "LENS_FOCUS_KIRK", "LENS_FOCUS_PLANE", "lens_from_kirk", "camera_rays_host", "hair_eval_host", "hair_sample_host",
-           "env_light_tables_host", "env_light_sample_host", "env_light_eval_host", "kmath_host"]
+           "env_light_tables_host", "env_light_sample_host", "env_light_eval_host", "kmath_host", "refit_host"]

@@ -1162,17 +1162,23 @@ __global__ void k_lay_slots(const uint32_t* ids, uint32_t N, const uint32_t* P, 
 
 }  // namespace gb
 
-std::string device_layout(const DeviceObjects& o, DeviceTree& t, hipStream_t st, DevMem& dnodes, DevMem& prims,
-                          DevMem& aux, DeviceLayout& out, double* kernel_ms) {
-    using namespace gb;
-    const uint32_t N = o.n_obj, n = t.n_nodes, nl = t.n_leaves;
+namespace gb {
+
+// The maps of the layout: rec_of (BuildNode -> record), and per leaf (preorder ordinal) its first
+// position, candidate-count function and first slot; Htot pair-opening nodes, stot.x slots.
+struct LayMaps {
+    Buf h, H, rec_of, lfirst, lfun, lscan, slot0, tmp;
+    uint32_t Htot = 0;
+    uint2 stot{0, 0};
+    BuildNode root{};
+};
+
+static std::string layout_maps(const DeviceTree& t, hipStream_t st, LayMaps& m) {
+    const uint32_t n = t.n_nodes, nl = t.n_leaves;
     const BuildNode* fin = t.nodes.as<BuildNode>();
     const uint32_t* P = t.P.as<uint32_t>();
-    Buf h, H, rec_of, lfirst, lfun, lscan, slot0, tmp;
-    hipEvent_t ev0, ev1;
-    GBCHK(hipEventCreate(&ev0));
-    GBCHK(hipEventCreate(&ev1));
-    GBCHK(hipEventRecord(ev0, st));
+    Buf &h = m.h, &H = m.H, &rec_of = m.rec_of, &lfirst = m.lfirst, &lfun = m.lfun, &lscan = m.lscan, &slot0 = m.slot0,
+        &tmp = m.tmp;
     GBCHK(h.ensure(4 * ((size_t)n + 1)));
     GBCHK(H.ensure(4 * ((size_t)n + 1)));
     GBCHK(rec_of.ensure(4 * (size_t)n));
@@ -1200,13 +1206,32 @@ std::string device_layout(const DeviceObjects& o, DeviceTree& t, hipStream_t st,
     hipLaunchKernelGGL(k_lay_slot0, dim3(blocks(nl, 256)), dim3(256), 0, st, lfun.as<uint2>(), lscan.as<uint2>(), nl,
                        slot0.as<uint32_t>());
     GBCHK(hipGetLastError());
-    uint32_t Htot = 0;
-    uint2 stot{0, 0};
-    BuildNode root{};
-    GBCHK(hipMemcpyAsync(&Htot, H.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st));
-    GBCHK(hipMemcpyAsync(&stot, lscan.as<uint2>() + nl, 8, hipMemcpyDeviceToHost, st));
-    GBCHK(hipMemcpyAsync(&root, fin, sizeof(BuildNode), hipMemcpyDeviceToHost, st));
+    GBCHK(hipMemcpyAsync(&m.Htot, H.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st));
+    GBCHK(hipMemcpyAsync(&m.stot, lscan.as<uint2>() + nl, 8, hipMemcpyDeviceToHost, st));
+    GBCHK(hipMemcpyAsync(&m.root, fin, sizeof(BuildNode), hipMemcpyDeviceToHost, st));
     GBCHK(hipStreamSynchronize(st));
+    return std::string();
+}
+
+}  // namespace gb
+
+std::string device_layout(const DeviceObjects& o, DeviceTree& t, hipStream_t st, DevMem& dnodes, DevMem& prims,
+                          DevMem& aux, DeviceLayout& out, double* kernel_ms) {
+    using namespace gb;
+    const uint32_t N = o.n_obj, n = t.n_nodes;
+    const BuildNode* fin = t.nodes.as<BuildNode>();
+    const uint32_t* P = t.P.as<uint32_t>();
+    hipEvent_t ev0, ev1;
+    GBCHK(hipEventCreate(&ev0));
+    GBCHK(hipEventCreate(&ev1));
+    GBCHK(hipEventRecord(ev0, st));
+    LayMaps m;
+    std::string merr = layout_maps(t, st, m);
+    if (!merr.empty()) return merr;
+    Buf &rec_of = m.rec_of, &lfirst = m.lfirst, &lfun = m.lfun, &slot0 = m.slot0;
+    const uint32_t Htot = m.Htot;
+    const uint2 stot = m.stot;
+    const BuildNode root = m.root;
     const bool root_interior = root.count == 0;
     out.n_dnodes = root_interior ? 2u + 2u * Htot : 0u;
     out.n_slots = stot.x;
@@ -1238,6 +1263,261 @@ std::string device_layout(const DeviceObjects& o, DeviceTree& t, hipStream_t st,
     const float rb[6] = {root.mn.x, root.mn.y, root.mn.z, root.mx.x, root.mx.y, root.mx.z};
     memcpy(out.root_box, rb, sizeof(rb));
     GBCHK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    GBCHK(hipEventElapsedTime(&ms, ev0, ev1));
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+    if (kernel_ms) *kernel_ms = ms;
+    return std::string();
+}
+
+// ---- refit: the same topology over moved objects (khp_update_geometry) ------------
+// Visibility between a level and the one above it comes from the kernel boundary: the
+// XCDs' L2s are not coherent, and a single-launch climb with a per-node arrival counter
+// would pay an agent-scope release / acquire per node where this pays one launch per level.
+namespace gb {
+
+constexpr uint32_t DEPTH_LEAF = 0xffu;  // sort key of a leaf: behind every interior level (depth < STACK_MAX)
+
+__global__ void k_plan_parent(const BuildNode* fin, uint32_t n, int32_t* parent) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (i == 0) parent[0] = -1;
+    const BuildNode nd = fin[i];
+    if (nd.count != 0) return;
+    if ((uint32_t)nd.left < n) parent[nd.left] = (int32_t)i;
+    if ((uint32_t)nd.right < n) parent[nd.right] = (int32_t)i;
+}
+
+// depth = hops to the root (at most max_depth); hist[d] counts the interior nodes of depth d
+__global__ void k_plan_depth(const BuildNode* fin, uint32_t n, const int32_t* parent, uint32_t max_depth,
+                             uint32_t* key, uint32_t* val, uint32_t* hist) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t d = 0;
+    for (int32_t j = parent[i]; j >= 0 && (uint32_t)j < n && d <= max_depth; j = parent[j]) ++d;
+    val[i] = i;
+    if (fin[i].count != 0) {
+        key[i] = DEPTH_LEAF;
+    } else {
+        key[i] = d < DEPTH_LEAF ? d : DEPTH_LEAF - 1u;
+        atomicAdd(hist + (d < DEPTH_LEAF ? d : DEPTH_LEAF - 1u), 1u);
+    }
+}
+
+// position p of the leaf order -> its slot (k_lay_slots' rule)
+__global__ void k_plan_slots(uint32_t N, const uint32_t* P, uint32_t nl, const uint32_t* lfirst, const uint32_t* slot0,
+                             uint32_t* slot_of) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N) return;
+    const uint32_t l = P[p + 1] - 1u;
+    slot_of[p] = l < nl ? slot0[l] + (p - lfirst[l]) : 0xffffffffu;  // k_refit_slots skips a slot out of range
+}
+
+// one thread per leaf: the union of its objects' bounds in the order of ids (k_level_leaves)
+__global__ void k_refit_leaves(BuildNode* fin, uint32_t n, const uint32_t* __restrict__ leaves, uint32_t n_leaves,
+                               const uint32_t* __restrict__ ids, uint32_t N, const float* __restrict__ bounds) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_leaves) return;
+    const uint32_t i = leaves[k];
+    if (i >= n) return;
+    const int32_t first = fin[i].first, count = fin[i].count;
+    if (count <= 0 || first < 0 || (uint32_t)first + (uint32_t)count > N) return;
+    GBox bv = box_empty();
+    for (int32_t p = first; p < first + count; ++p) {
+        const uint32_t o = ids[p];
+        if (o >= N) continue;
+        const float* bb = &bounds[6 * (size_t)o];
+        bv.mn[0] = smin(bv.mn[0], bb[0]); bv.mn[1] = smin(bv.mn[1], bb[1]); bv.mn[2] = smin(bv.mn[2], bb[2]);
+        bv.mx[0] = smax(bv.mx[0], bb[3]); bv.mx[1] = smax(bv.mx[1], bb[4]); bv.mx[2] = smax(bv.mx[2], bb[5]);
+    }
+    fin[i].mn = mk(bv.mn[0], bv.mn[1], bv.mn[2]);
+    fin[i].mx = mk(bv.mx[0], bv.mx[1], bv.mx[2]);
+}
+
+// one level of interior nodes: union(left, right) in that order (k_level_interior)
+__global__ void k_refit_level(BuildNode* fin, uint32_t n, const uint32_t* __restrict__ order, uint32_t cnt) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= cnt) return;
+    const uint32_t i = order[k];
+    if (i >= n) return;
+    const int32_t l = fin[i].left, r = fin[i].right;
+    if (fin[i].count != 0 || l < 0 || r < 0 || (uint32_t)l >= n || (uint32_t)r >= n) return;
+    const BuildNode L = fin[l], R = fin[r];
+    GBox bv = box_empty();
+    grow(bv, GBox{{L.mn.x, L.mn.y, L.mn.z}, {L.mx.x, L.mx.y, L.mx.z}});
+    grow(bv, GBox{{R.mn.x, R.mn.y, R.mn.z}, {R.mx.x, R.mx.y, R.mx.z}});
+    fin[i].mn = mk(bv.mn[0], bv.mn[1], bv.mn[2]);
+    fin[i].mx = mk(bv.mx[0], bv.mx[1], bv.mx[2]);
+}
+
+// the box words of the 64-B records (k_lay_nodes); refs and counts stay
+__global__ void k_refit_records(const BuildNode* __restrict__ fin, uint32_t n, const int32_t* __restrict__ rec_of,
+                                uint32_t n_dnodes, DevNode* dn) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const BuildNode nd = fin[i];
+    if (nd.count != 0) return;
+    const int32_t r = rec_of[i];
+    if (r < 0 || (uint32_t)r >= n_dnodes || (uint32_t)nd.left >= n || (uint32_t)nd.right >= n) return;
+    const BuildNode L = fin[nd.left], R = fin[nd.right];
+    float4* d = (float4*)(dn + r);
+    d[0] = make_float4(L.mn.x, L.mn.y, L.mn.z, L.mx.x);
+    d[1] = make_float4(L.mx.y, L.mx.z, R.mn.x, R.mn.y);
+    d[2] = make_float4(R.mn.z, R.mx.x, R.mx.y, R.mx.z);
+}
+
+// the slot-ordered primitive records and base_d (k_lay_slots); mat, obj and flags stay
+__global__ void k_refit_slots(const uint32_t* __restrict__ ids, uint32_t N, const uint32_t* __restrict__ slot_of,
+                              uint32_t n_slots, const float4* __restrict__ rec_obj, const Aux* __restrict__ aux_obj,
+                              float4* prims, Aux* aux) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N) return;
+    const uint32_t s = slot_of[p], o = ids[p];
+    if (s >= n_slots || o >= N) return;
+    const float4* src = rec_obj + 4 * (size_t)o;
+    float4* dst = prims + 4 * (size_t)s;
+    dst[0] = src[0];
+    dst[1] = src[1];
+    dst[2] = src[2];
+    dst[3] = src[3];
+    aux[s].base_d = aux_obj[o].base_d;
+}
+
+// SAH terms in double, reduced per block in a fixed order; the host adds the block sums in block order
+__global__ __launch_bounds__(256) void k_refit_sah(const BuildNode* __restrict__ fin, uint32_t n, double* partial) {
+    __shared__ double sh[256];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    double v = 0.0;
+    if (i < n) {
+        const BuildNode nd = fin[i];
+        const double sx = (double)nd.mx.x - (double)nd.mn.x, sy = (double)nd.mx.y - (double)nd.mn.y,
+                     sz = (double)nd.mx.z - (double)nd.mn.z;
+        const double a = 2.0 * (sx * sy + sx * sz + sy * sz);
+        v = nd.count != 0 ? (double)nd.count * a : a;
+    }
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (uint32_t s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+}
+
+// the reduction kernel; ev (optional) is recorded behind it, before the block sums leave the device
+static std::string refit_sah(const DeviceTree& t, RefitPlan& plan, hipStream_t st, float root_box[6], double* cost,
+                             hipEvent_t ev = nullptr) {
+    const uint32_t n = t.n_nodes, nb = blocks(n, 256);
+    hipLaunchKernelGGL(k_refit_sah, dim3(nb), dim3(256), 0, st, t.nodes.as<BuildNode>(), n, plan.partial.as<double>());
+    GBCHK(hipGetLastError());
+    if (ev) GBCHK(hipEventRecord(ev, st));
+    std::vector<double> part(nb);
+    BuildNode root{};
+    GBCHK(hipMemcpyAsync(part.data(), plan.partial.p, 8 * (size_t)nb, hipMemcpyDeviceToHost, st));
+    GBCHK(hipMemcpyAsync(&root, t.nodes.p, sizeof(BuildNode), hipMemcpyDeviceToHost, st));
+    GBCHK(hipStreamSynchronize(st));
+    double sum = 0.0;
+    for (uint32_t b = 0; b < nb; ++b) sum += part[b];
+    const double sx = (double)root.mx.x - (double)root.mn.x, sy = (double)root.mx.y - (double)root.mn.y,
+                 sz = (double)root.mx.z - (double)root.mn.z;
+    const double a0 = 2.0 * (sx * sy + sx * sz + sy * sz);
+    *cost = a0 > 0.0 ? sum / a0 : 0.0;
+    if (root_box) {
+        const float rb[6] = {root.mn.x, root.mn.y, root.mn.z, root.mx.x, root.mx.y, root.mx.z};
+        memcpy(root_box, rb, sizeof(rb));
+    }
+    return std::string();
+}
+
+}  // namespace gb
+
+std::string device_refit_plan(const DeviceObjects& o, const DeviceTree& t, uint32_t max_depth, hipStream_t st,
+                              RefitPlan& plan) {
+    using namespace gb;
+    plan.release();
+    const uint32_t N = o.n_obj, n = t.n_nodes;
+    if (n == 0 || N == 0) return "no tree";
+    const BuildNode* fin = t.nodes.as<BuildNode>();
+    LayMaps m;
+    std::string merr = layout_maps(t, st, m);
+    if (!merr.empty()) return merr;
+    GBCHK(plan.rec_of.ensure(4 * (size_t)n));
+    GBCHK(plan.slot_of.ensure(4 * (size_t)N));
+    GBCHK(plan.partial.ensure(8 * (size_t)blocks(n, 256)));
+    GBCHK(hipMemcpyAsync(plan.rec_of.p, m.rec_of.p, 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_plan_slots, dim3(blocks(N, 256)), dim3(256), 0, st, N, t.P.as<uint32_t>(),
+                       t.n_leaves, m.lfirst.as<uint32_t>(), m.slot0.as<uint32_t>(), plan.slot_of.as<uint32_t>());
+    // parents, depths, and the interior nodes sorted by depth (leaves sort behind them)
+    Buf parent, key, key2, val, val2, hist, tmp;
+    GBCHK(parent.ensure(4 * (size_t)n));
+    GBCHK(key.ensure(4 * (size_t)n));
+    GBCHK(key2.ensure(4 * (size_t)n));
+    GBCHK(val.ensure(4 * (size_t)n));
+    GBCHK(val2.ensure(4 * (size_t)n));
+    GBCHK(hist.ensure(4 * 256));
+    GBCHK(hipMemsetAsync(hist.p, 0, 4 * 256, st));
+    hipLaunchKernelGGL(k_plan_parent, dim3(blocks(n, 256)), dim3(256), 0, st, fin, n, parent.as<int32_t>());
+    hipLaunchKernelGGL(k_plan_depth, dim3(blocks(n, 256)), dim3(256), 0, st, fin, n, parent.as<int32_t>(), max_depth,
+                       key.as<uint32_t>(), val.as<uint32_t>(), hist.as<uint32_t>());
+    GBCHK(hipGetLastError());
+    size_t tb = 0;
+    GBCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                             (uint32_t*)nullptr, (int)n, 0, 8, st));
+    GBCHK(tmp.ensure(tb));
+    GBCHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, key.as<uint32_t>(), key2.as<uint32_t>(), val.as<uint32_t>(),
+                                             val2.as<uint32_t>(), (int)n, 0, 8, st));
+    uint32_t h[256];
+    GBCHK(hipMemcpyAsync(h, hist.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    GBCHK(hipStreamSynchronize(st));
+    const uint32_t n_int = n - t.n_leaves;
+    plan.level_start.assign(1, 0u);
+    uint32_t tot = 0;
+    for (uint32_t d = 0; d < DEPTH_LEAF && tot < n_int; ++d) {
+        tot += h[d];
+        plan.level_start.push_back(tot);
+    }
+    if (tot != n_int) return "refit plan: the depth histogram does not cover the interior nodes";
+    GBCHK(plan.order.ensure(4 * (size_t)n));   // the leaves follow the interior levels: k_refit_leaves' list
+    GBCHK(hipMemcpyAsync(plan.order.p, val2.p, 4 * (size_t)n, hipMemcpyDeviceToDevice, st));
+    std::string e = refit_sah(t, plan, st, nullptr, &plan.sah_built);
+    if (!e.empty()) return e;
+    plan.valid = true;
+    return std::string();
+}
+
+std::string device_refit(const DeviceObjects& o, DeviceTree& t, RefitPlan& plan, hipStream_t st, DevMem& dnodes,
+                         DevMem& prims, DevMem& aux, uint32_t n_dnodes, uint32_t n_slots, float root_box[6],
+                         double* sah_cost, double* kernel_ms) {
+    using namespace gb;
+    if (!plan.valid) return "refit without a plan";
+    const uint32_t N = o.n_obj, n = t.n_nodes;
+    BuildNode* fin = t.nodes.as<BuildNode>();
+    if (sizeof(DevNode) * (size_t)n_dnodes > dnodes.bytes || 64 * (size_t)n_slots > prims.bytes ||
+        sizeof(Aux) * (size_t)n_slots > aux.bytes)
+        return "refit: the layout's counts exceed its buffers";
+    hipEvent_t ev0, ev1;
+    GBCHK(hipEventCreate(&ev0));
+    GBCHK(hipEventCreate(&ev1));
+    GBCHK(hipEventRecord(ev0, st));
+    const uint32_t n_int = plan.level_start.back();
+    hipLaunchKernelGGL(k_refit_leaves, dim3(blocks(n - n_int, 256)), dim3(256), 0, st, fin, n,
+                       plan.order.as<uint32_t>() + n_int, n - n_int, t.ids.as<uint32_t>(), N, o.bounds.as<float>());
+    for (size_t d = plan.level_start.size() - 1; d-- > 0;) {
+        const uint32_t lo = plan.level_start[d], cnt = plan.level_start[d + 1] - lo;
+        if (cnt)
+            hipLaunchKernelGGL(k_refit_level, dim3(blocks(cnt, 256)), dim3(256), 0, st, fin, n,
+                               plan.order.as<uint32_t>() + lo, cnt);
+    }
+    if (n > 1)
+        hipLaunchKernelGGL(k_refit_records, dim3(blocks(n, 256)), dim3(256), 0, st, fin, n, plan.rec_of.as<int32_t>(),
+                           n_dnodes, dnodes.as<DevNode>());
+    hipLaunchKernelGGL(k_refit_slots, dim3(blocks(N, 256)), dim3(256), 0, st, t.ids.as<uint32_t>(), N,
+                       plan.slot_of.as<uint32_t>(), n_slots, o.rec.as<float4>(), o.aux.as<Aux>(), prims.as<float4>(),
+                       aux.as<Aux>());
+    GBCHK(hipGetLastError());
+    std::string e = refit_sah(t, plan, st, root_box, sah_cost, ev1);   // synchronises the stream
+    if (!e.empty()) return e;
     float ms = 0.0f;
     GBCHK(hipEventElapsedTime(&ms, ev0, ev1));
     (void)hipEventDestroy(ev0);

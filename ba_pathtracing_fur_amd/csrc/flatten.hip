@@ -23,7 +23,8 @@ __device__ __forceinline__ bool all_finite(v3 a, v3 b, v3 c) {
 }
 
 // err bits: 1 triangle material, 2 cone material, 4 cone model, 8 tri_v, 16 cone_base_r0,
-// 32 cone_apex_r1 not finite, 64 finite geometry whose box or centroid overflows float32
+// 32 cone_apex_r1 not finite, 64 finite geometry whose box or centroid overflows float32.
+// tm / cm null: the geometry part alone (device_reflatten), the aux words' mat / obj / flags kept.
 __global__ void k_flatten_tris(const float* __restrict__ tv, const float* __restrict__ tn,
                                const uint32_t* __restrict__ tm, const float* __restrict__ uv_in, uint32_t n_tris,
                                uint32_t n_mat, float4* rec, Aux* aux, float* bounds, float* cen, float* nrm,
@@ -42,10 +43,11 @@ __global__ void k_flatten_tris(const float* __restrict__ tv, const float* __rest
     o[1] = make_float4(r[4], r[5], r[6], r[7]);
     o[2] = make_float4(r[8], r[9], r[10], r[11]);
     o[3] = make_float4(r[12], r[13], r[14], r[15]);
-    const uint32_t m = tm[i];
-    if (m >= n_mat) atomicOr(err, 1u);
     if (!all_finite(ld3(v), ld3(v + 3), ld3(v + 6))) atomicOr(err, 8u);
     else if (!all_finite(ld3(bnd), ld3(bnd + 3), ld3(ce))) atomicOr(err, 64u);
+    if (!tm) return;  // geometry only (device_reflatten): a triangle's aux word holds none
+    const uint32_t m = tm[i];
+    if (m >= n_mat) atomicOr(err, 1u);
     aux[i] = Aux{0.0f, m, i, 0u};
 }
 
@@ -81,13 +83,17 @@ __global__ void k_flatten_cones(const float4* __restrict__ b, const float4* __re
     o[1] = make_float4(r[4], r[5], r[6], r[7]);
     o[2] = make_float4(r[8], r[9], r[10], r[11]);
     o[3] = make_float4(r[12], r[13], r[14], r[15]);
-    const uint32_t m = cm[i];
-    if (m >= n_mat) atomicOr(err, 2u);
     const bool base_ok = all_finite(base, mk(bb.w, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f));
     const bool apex_ok = all_finite(apex, mk(aa.w, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f));
     if (!base_ok) atomicOr(err, 16u);
     if (!apex_ok) atomicOr(err, 32u);
     if (base_ok && apex_ok && !all_finite(ld3(bnd), ld3(bnd + 3), ld3(ce))) atomicOr(err, 64u);
+    if (!cm) {  // geometry only (device_reflatten): mat, obj and flags stay as khp_set_scene left them
+        aux[id].base_d = base_d;
+        return;
+    }
+    const uint32_t m = cm[i];
+    if (m >= n_mat) atomicOr(err, 2u);
     aux[id] = Aux{base_d, m, id, 1u};
 }
 
@@ -254,10 +260,26 @@ std::string device_flatten(const khp_scene* s, bool device_ptrs, uint32_t n_mate
         o.tri_uv.release();
         o.cone_h.release();
     }
-    DevMem tv, tn, tm, tuv, cb, ca, cm, cmod, dmodels, err;
+    DevMem tv, tn, tm, cb, ca, cm, dmodels, err;
     const float *dtv = s->tri_v, *dtn = s->tri_n, *dcb = s->cone_base_r0, *dca = s->cone_apex_r1;
     const float* duv = textured ? s->tri_uv : nullptr;
     const uint32_t *dtm = s->tri_mat, *dcm = s->cone_mat, *dcmod = s->cone_model;
+    // the texcoords as the caller gave them stay in HBM: the ctor's reordering follows the
+    // vertices, so a later device_reflatten redoes it from the source
+    o.tri_uv_src.release();
+    if (duv && nt) {
+        FLCHK(o.tri_uv_src.ensure(24 * (size_t)nt));
+        FLCHK(hipMemcpyAsync(o.tri_uv_src.p, s->tri_uv, 24 * (size_t)nt,
+                             device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        duv = o.tri_uv_src.as<float>();
+    }
+    o.cone_model.release();   // likewise the per-cone model indices of a scene with cone models
+    if (!models.empty() && dcmod && nc) {
+        FLCHK(o.cone_model.ensure(4 * (size_t)nc));
+        FLCHK(hipMemcpyAsync(o.cone_model.p, s->cone_model, 4 * (size_t)nc,
+                             device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        dcmod = o.cone_model.as<uint32_t>();
+    }
     if (!models.empty()) {
         FLCHK(dmodels.ensure(4 * models.size()));
         FLCHK(hipMemcpyAsync(dmodels.p, models.data(), 4 * models.size(), hipMemcpyHostToDevice, st));
@@ -273,11 +295,6 @@ std::string device_flatten(const khp_scene* s, bool device_ptrs, uint32_t n_mate
             dtv = tv.as<float>();
             dtn = tn.as<float>();
             dtm = tm.as<uint32_t>();
-            if (duv) {
-                FLCHK(tuv.ensure(24 * (size_t)nt));
-                FLCHK(hipMemcpyAsync(tuv.p, s->tri_uv, 24 * (size_t)nt, hipMemcpyHostToDevice, st));
-                duv = tuv.as<float>();
-            }
         }
         if (nc) {
             FLCHK(cb.ensure(16 * (size_t)nc));
@@ -289,11 +306,6 @@ std::string device_flatten(const khp_scene* s, bool device_ptrs, uint32_t n_mate
             dcb = cb.as<float>();
             dca = ca.as<float>();
             dcm = cm.as<uint32_t>();
-            if (s->cone_model) {
-                FLCHK(cmod.ensure(4 * (size_t)nc));
-                FLCHK(hipMemcpyAsync(cmod.p, s->cone_model, 4 * (size_t)nc, hipMemcpyHostToDevice, st));
-                dcmod = cmod.as<uint32_t>();
-            }
         }
     }
     FLCHK(err.ensure(4));
@@ -344,6 +356,74 @@ std::string device_flatten(const khp_scene* s, bool device_ptrs, uint32_t n_mate
     if (herr & 32u) return "EINVAL:cone_apex_r1 holds a NaN or an infinity";
     if (herr & 64u) return "EINVAL:an object's bounds or centroid overflow float32";
     if (herr & 128u) return "EINVAL:a triangle's material is a ChiangHairBSDF: the kind needs a cone's axis and radius";
+    return std::string();
+}
+
+std::string device_reflatten(const khp_scene* s, bool device_ptrs, bool textured, const std::vector<float>& models,
+                             DeviceObjects& o, hipStream_t st, double* kernel_ms) {
+    using namespace fl;
+    const uint32_t nt = o.n_tris, nc = o.n_cones;  // the caller checked s->n_tris / s->n_cones against them
+    if (s->tri_frame && nt)
+        FLCHK(hipMemcpyAsync(o.tri_frame.p, s->tri_frame, 36 * (size_t)nt,
+                             device_ptrs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    else
+        FLCHK(hipMemsetAsync(o.tri_frame.p, 0, 36 * (size_t)std::max(nt, 1u), st));
+    DevMem tv, tn, cb, ca, dmodels, err;
+    const float *dtv = s->tri_v, *dtn = s->tri_n, *dcb = s->cone_base_r0, *dca = s->cone_apex_r1;
+    if (!models.empty()) {
+        FLCHK(dmodels.ensure(4 * models.size()));
+        FLCHK(hipMemcpyAsync(dmodels.p, models.data(), 4 * models.size(), hipMemcpyHostToDevice, st));
+    }
+    if (!device_ptrs) {
+        if (nt) {
+            FLCHK(tv.ensure(36 * (size_t)nt));
+            FLCHK(tn.ensure(36 * (size_t)nt));
+            FLCHK(hipMemcpyAsync(tv.p, s->tri_v, 36 * (size_t)nt, hipMemcpyHostToDevice, st));
+            FLCHK(hipMemcpyAsync(tn.p, s->tri_n, 36 * (size_t)nt, hipMemcpyHostToDevice, st));
+            dtv = tv.as<float>();
+            dtn = tn.as<float>();
+        }
+        if (nc) {
+            FLCHK(cb.ensure(16 * (size_t)nc));
+            FLCHK(ca.ensure(16 * (size_t)nc));
+            FLCHK(hipMemcpyAsync(cb.p, s->cone_base_r0, 16 * (size_t)nc, hipMemcpyHostToDevice, st));
+            FLCHK(hipMemcpyAsync(ca.p, s->cone_apex_r1, 16 * (size_t)nc, hipMemcpyHostToDevice, st));
+            dcb = cb.as<float>();
+            dca = ca.as<float>();
+        }
+    }
+    FLCHK(err.ensure(4));
+    FLCHK(hipMemsetAsync(err.p, 0, 4, st));
+    hipEvent_t e0, e1;
+    FLCHK(hipEventCreate(&e0));
+    FLCHK(hipEventCreate(&e1));
+    FLCHK(hipEventRecord(e0, st));
+    if (nt)
+        hipLaunchKernelGGL(k_flatten_tris, dim3(blocks(nt, 256)), dim3(256), 0, st, dtv, dtn, (const uint32_t*)nullptr,
+                           (const float*)o.tri_uv_src.as<float>(), nt, 0u, o.rec.as<float4>(), o.aux.as<Aux>(),
+                           o.bounds.as<float>(), o.centroid.as<float>(), o.tri_nrm.as<float>(),
+                           textured ? o.tri_uv.as<float>() : nullptr, err.as<uint32_t>());
+    if (nc)
+        hipLaunchKernelGGL(k_flatten_cones, dim3(blocks(nc, 256)), dim3(256), 0, st, (const float4*)dcb,
+                           (const float4*)dca, (const uint32_t*)nullptr,
+                           models.empty() ? nullptr : (const uint32_t*)o.cone_model.as<uint32_t>(),
+                           models.empty() ? nullptr : (const float*)dmodels.as<float>(), (uint32_t)(models.size() / 25),
+                           nc, nt, 0u, o.rec.as<float4>(), o.aux.as<Aux>(), o.bounds.as<float>(),
+                           o.centroid.as<float>(), textured ? o.cone_h.as<float>() : nullptr, err.as<uint32_t>());
+    FLCHK(hipGetLastError());
+    FLCHK(hipEventRecord(e1, st));
+    uint32_t herr = 0;
+    FLCHK(hipMemcpyAsync(&herr, err.p, 4, hipMemcpyDeviceToHost, st));
+    FLCHK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    FLCHK(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (kernel_ms) *kernel_ms = ms;
+    if (herr & 8u) return "EINVAL:tri_v holds a NaN or an infinity";
+    if (herr & 16u) return "EINVAL:cone_base_r0 holds a NaN or an infinity";
+    if (herr & 32u) return "EINVAL:cone_apex_r1 holds a NaN or an infinity";
+    if (herr & 64u) return "EINVAL:an object's bounds or centroid overflow float32";
     return std::string();
 }
 

@@ -2830,6 +2830,11 @@ struct khp_ctx {
     DeviceTree tree;          // device-built BVH (preorder nodes, ids), kept for khp_read_bvh
     bool tree_on_device = false;
     uint32_t n_dnodes = 0, n_slots = 0;
+    // khp_update_geometry: the device-built tree is there to refit (kept through a refused update that
+    // leaves the context un-built); the plan, made by the first update after a build; the last info
+    bool can_refit = false;
+    RefitPlan refit;
+    khp_refit_info refit_info{};
     DevMem fb, pix, stage, stage_pix, snap;   // snap: per-bounce Counters snapshots (stats renders)
     DevMem pixheavy;                          // path_order 2: per image pixel, its last camera ray was long
     int cur_bounce = -1;
@@ -3398,6 +3403,7 @@ static khp_status set_scene_impl(khp_ctx* c, const khp_scene* s, bool device_ptr
                                                   : "a ChiangHairBSDF material with hair lobes other than R: khp_set_hair_lobes(R) first");
     c->scene_set = false;
     c->built = false;
+    c->can_refit = false;
     ++c->gen;
     std::string err = flatten_scene(s, c->hs, host);
     if (!err.empty()) return fail(KHP_EINVAL, err);
@@ -3533,6 +3539,9 @@ extern "C" khp_status khp_build_accel(khp_ctx* c) {
     const bool host_build = c->scene_on_host;  // the path khp_set_scene flattened on
     HostScene& hs = c->hs;
     c->built = false;
+    c->can_refit = false;
+    c->refit.release();
+    c->refit_info = khp_refit_info{};
     c->st.bvh_kernel_ms = 0.0;
     c->st.bvh_on_device = host_build ? 0u : 1u;
     double lay_kernel_ms = 0.0;
@@ -3720,7 +3729,116 @@ extern "C" khp_status khp_build_accel(khp_ctx* c) {
     else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_path<false, true, KINDS_ALL, true>), TRAV_BLOCK, PATH_LDS));
     c->grid_path_w = std::min(c->grid_path, std::max(1, nb) * c->n_cu);   // the columns are sized by grid_path
     c->built = true;
+    c->can_refit = !host_build;
     ++c->gen;
+    return KHP_OK;
+}
+
+// ---- khp_update_geometry: re-flatten, refit, remake the derived records -----------------
+// What reads geometry-derived state and is refreshed here: c->obj (records, bounds, centroids,
+// tri_nrm, tri_frame, tri_uv, cone_h: S points into them), c->tree's boxes, the box words of c->nodes,
+// c->prims and base_d of c->aux, c->wide, c->topn, S.root_box (the traversal's root slab and the
+// origin-cell regrouping read it from the S each launch is given).  c->trislot maps a triangle to its
+// slot: topology.  The light-path variant and the environment light read lights and the map, no geometry.
+static khp_status refit_plan_ready(khp_ctx* c) {
+    if (c->refit.valid) return KHP_OK;
+    std::string err = device_refit_plan(c->obj, c->tree, c->hs.depth, c->stream, c->refit);
+    if (!err.empty()) return fail(KHP_EDEVICE, err);
+    c->refit_info.sah_cost = c->refit_info.sah_cost_built = c->refit.sah_built;
+    memcpy(c->refit_info.root_box, c->S.root_box, sizeof(c->refit_info.root_box));
+    return KHP_OK;
+}
+
+static khp_status update_geometry_impl(khp_ctx* c, const khp_scene* s, khp_refit_info* info, bool device_ptrs) {
+    if (!c || !s) return fail(KHP_EINVAL, "khp_update_geometry: ctx or moved is null");
+    HIPCHK(hipSetDevice(c->device));
+    khp_status dr = drain(c);  // frames in flight finish with the geometry they started with
+    if (dr != KHP_OK) return dr;
+    if (host_path(c)) return fail(KHP_EUNSUPPORTED, "khp_update_geometry: a KHP_CTX_HOST_BUILD context keeps no tree in HBM");
+    if (!c->can_refit) return fail(KHP_ENOTREADY, "khp_update_geometry: khp_build_accel first");
+    if (s->n_tris != c->obj.n_tris || s->n_cones != c->obj.n_cones)
+        return fail(KHP_EINVAL, "khp_update_geometry: n_tris / n_cones differ from the built scene's (" +
+                                    std::to_string(c->obj.n_tris) + " / " + std::to_string(c->obj.n_cones) + ")");
+    if (s->n_tris && (!s->tri_v || !s->tri_n)) return fail(KHP_EINVAL, "khp_update_geometry: triangle arrays missing");
+    if (s->n_cones && (!s->cone_base_r0 || !s->cone_apex_r1)) return fail(KHP_EINVAL, "khp_update_geometry: cone arrays missing");
+    auto t0 = std::chrono::steady_clock::now();
+    KHPCHK(refit_plan_ready(c));   // reads the tree as the build left it: before anything moves
+    // from here on the object arrays change: until the tree follows them the context is un-built
+    c->built = false;
+    c->scene_set = false;  // and khp_build_accel has no finite scene to build from
+    ++c->gen;
+    c->hs.nodes.clear();   // khp_read_bvh downloads the tree again
+    double flat_ms = 0.0, refit_ms = 0.0, cost = 0.0;
+    std::string err = device_reflatten(s, device_ptrs, c->hs.textured, c->hs.models, c->obj, c->stream, &flat_ms);
+    if (!err.empty()) {
+        if (err.rfind("EINVAL:", 0) == 0) return fail(KHP_EINVAL, err.substr(7));
+        return fail(KHP_EDEVICE, err);
+    }
+    float root_box[6];
+    err = device_refit(c->obj, c->tree, c->refit, c->stream, c->nodes, c->prims, c->aux, c->n_dnodes, c->n_slots,
+                       root_box, &cost, &refit_ms);
+    if (!err.empty()) return fail(KHP_EDEVICE, err);
+    struct Events {   // destroyed on every way out
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t x : e)
+                if (x) (void)hipEventDestroy(x);
+        }
+    } ev;
+    HIPCHK(hipEventCreate(&ev.e[0]));
+    HIPCHK(hipEventCreate(&ev.e[1]));
+    const hipEvent_t e0 = ev.e[0], e1 = ev.e[1];
+    HIPCHK(hipEventRecord(e0, c->stream));
+    if (c->S.wide && c->n_dnodes > 0) {   // a refit keeps each box the union of its children's: anything else is an error
+        HIPCHK(hipMemsetAsync(c->wide_bad.p, 0, sizeof(uint32_t), c->stream));
+        hipLaunchKernelGGL(k_wide_records, dim3((c->n_dnodes + 255) / 256), dim3(256), 0, c->stream,
+                           c->nodes.as<DevNode>(), c->n_dnodes, c->wide.as<float4>(), c->wide_bad.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+    }
+    if (c->n_dnodes > 0) {
+        hipLaunchKernelGGL(k_top_nodes, dim3(1), dim3(64), 0, c->stream, c->nodes.as<DevNode>(), c->S.root_ref,
+                           c->topn.as<DevNode>());
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(e1, c->stream));
+    uint32_t bad = 0;
+    if (c->S.wide && c->n_dnodes > 0)
+        HIPCHK(hipMemcpyAsync(&bad, c->wide_bad.p, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+    KHPCHK(wait_stream(c, c->stream, "the geometry update"));
+    if (bad) return fail(KHP_EDEVICE, "khp_update_geometry: a refitted box is not the union of its children's");
+    float tail_ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&tail_ms, e0, e1));
+    memcpy(c->S.root_box, root_box, sizeof(c->S.root_box));
+    c->scene_set = true;
+    c->built = true;
+    khp_refit_info& ri = c->refit_info;
+    ri.kernel_ms = flat_ms + refit_ms + (double)tail_ms;
+    ri.sah_cost = cost;
+    ri.sah_cost_built = c->refit.sah_built;
+    ri.n_updates += 1;
+    memcpy(ri.root_box, root_box, sizeof(ri.root_box));
+    ri.refit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (info) *info = ri;
+    return KHP_OK;
+}
+
+extern "C" khp_status khp_update_geometry(khp_ctx* c, const khp_scene* s, khp_refit_info* info) {
+    return update_geometry_impl(c, s, info, false);
+}
+
+extern "C" khp_status khp_update_geometry_device(khp_ctx* c, const khp_scene* s, khp_refit_info* info) {
+    return update_geometry_impl(c, s, info, true);
+}
+
+extern "C" khp_status khp_get_refit_info(khp_ctx* c, khp_refit_info* out) {
+    if (!c || !out) return fail(KHP_EINVAL, "khp_get_refit_info: null argument");
+    HIPCHK(hipSetDevice(c->device));
+    khp_status dr = drain(c);
+    if (dr != KHP_OK) return dr;
+    if (host_path(c)) return fail(KHP_EUNSUPPORTED, "khp_get_refit_info: a KHP_CTX_HOST_BUILD context keeps no tree in HBM");
+    if (!c->can_refit || !c->built) return fail(KHP_ENOTREADY, "khp_get_refit_info: khp_build_accel first");
+    KHPCHK(refit_plan_ready(c));
+    *out = c->refit_info;
     return KHP_OK;
 }
 

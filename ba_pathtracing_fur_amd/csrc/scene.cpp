@@ -605,6 +605,86 @@ extern "C" khp_status khp_host_build(const khp_scene* scene, uint32_t* n_nodes, 
     return KHP_OK;
 }
 
+// The host twin of khp_update_geometry (bvh_build.hip device_refit): leaf boxes in the
+// order of ids, then one reverse-preorder sweep -- in preorder the right child follows
+// the whole left subtree, so when node i is reached the stack holds its two children on top.
+extern "C" khp_status khp_refit_host(const khp_scene* moved, uint32_t n_nodes, const int32_t* node_first,
+                                     const int32_t* node_count, const int32_t* object_ids, float* node_boxes,
+                                     float* obj_bounds, float* records, double* sah_cost) {
+    if (!moved || !node_first || !node_count || !object_ids)
+        return fail(KHP_EINVAL, "khp_refit_host: moved, node_first, node_count or object_ids is null");
+    HostScene hs;
+    std::string err = flatten_scene(moved, hs);
+    if (!err.empty()) return fail(KHP_EINVAL, err);
+    const uint32_t N = hs.n_obj;
+    // the counts describe a preorder binary tree whose leaves tile object_ids in order
+    uint64_t next_first = 0;
+    int64_t open = 1;  // nodes still expected
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        if (open <= 0) return fail(KHP_EINVAL, "khp_refit_host: n_nodes does not match the counts (nodes after the tree ends)");
+        const int32_t cnt = node_count[i];
+        if (cnt < 0) return fail(KHP_EINVAL, "khp_refit_host: a negative node_count");
+        if (cnt == 0) {
+            open += 1;  // one node taken, two children owed
+        } else {
+            if (node_first[i] < 0 || (uint64_t)node_first[i] != next_first || next_first + (uint64_t)cnt > N)
+                return fail(KHP_EINVAL, "khp_refit_host: the leaf ranges do not tile object_ids in preorder");
+            next_first += (uint64_t)cnt;
+            open -= 1;
+        }
+    }
+    if (n_nodes == 0 || open != 0 || next_first != N)
+        return fail(KHP_EINVAL, "khp_refit_host: n_nodes does not match the counts (the tree is incomplete)");
+    for (uint32_t p = 0; p < N; ++p)
+        if (object_ids[p] < 0 || (uint32_t)object_ids[p] >= N)
+            return fail(KHP_EINVAL, "khp_refit_host: object id out of range");
+    std::vector<Box> box(n_nodes);
+    std::vector<uint32_t> stack;
+    double sum = 0.0;
+    auto area_d = [](const Box& b) {
+        const double sx = (double)b.mx.x - (double)b.mn.x, sy = (double)b.mx.y - (double)b.mn.y,
+                     sz = (double)b.mx.z - (double)b.mn.z;
+        return 2.0 * (sx * sy + sx * sz + sy * sz);
+    };
+    for (uint32_t i = n_nodes; i-- > 0;) {
+        Box b = box_empty();
+        if (node_count[i] > 0) {
+            for (int32_t p = node_first[i]; p < node_first[i] + node_count[i]; ++p) {
+                const float* bb = &hs.bounds[6 * (size_t)object_ids[p]];
+                grow(b, Box{mk(bb[0], bb[1], bb[2]), mk(bb[3], bb[4], bb[5])});
+            }
+            sum += (double)node_count[i] * area_d(b);
+        } else {
+            const uint32_t l = stack.back();
+            stack.pop_back();
+            const uint32_t r = stack.back();
+            stack.pop_back();
+            grow(b, box[l]);
+            grow(b, box[r]);
+            sum += area_d(b);
+        }
+        box[i] = b;
+        stack.push_back(i);
+    }
+    if (node_boxes)
+        for (uint32_t i = 0; i < n_nodes; ++i) {
+            const float b[6] = {box[i].mn.x, box[i].mn.y, box[i].mn.z, box[i].mx.x, box[i].mx.y, box[i].mx.z};
+            memcpy(node_boxes + 6 * (size_t)i, b, sizeof(b));
+        }
+    for (uint32_t i = 0; i < N; ++i) {
+        if (obj_bounds) {
+            memcpy(obj_bounds + 9 * (size_t)i, &hs.bounds[6 * (size_t)i], 6 * sizeof(float));
+            memcpy(obj_bounds + 9 * (size_t)i + 6, &hs.centroid[3 * (size_t)i], 3 * sizeof(float));
+        }
+        if (records) memcpy(records + 16 * (size_t)i, &hs.rec[16 * (size_t)i], 16 * sizeof(float));
+    }
+    if (sah_cost) {
+        const double a0 = area_d(box[0]);
+        *sah_cost = a0 > 0.0 ? sum / a0 : 0.0;
+    }
+    return KHP_OK;
+}
+
 extern "C" khp_status khp_gather_plan(uint32_t width, uint32_t height, uint32_t tile_size, int nranks, int rank,
                                       int root, uint64_t* counts, uint32_t* pixels, uint64_t* n_pixels) {
     if (!n_pixels) return fail(KHP_EINVAL, "khp_gather_plan: n_pixels is null");

@@ -347,6 +347,18 @@ class FurParams(ctypes.Structure):
         return p
 
 
+class RefitInfo(ctypes.Structure):
+    """khp_refit_info (khp_update_geometry)."""
+    _fields_ = [("refit_ms", ctypes.c_double), ("kernel_ms", ctypes.c_double), ("sah_cost", ctypes.c_double),
+                ("sah_cost_built", ctypes.c_double), ("n_updates", c_uint32), ("reserved", c_uint32),
+                ("root_box", c_float * 6)]
+
+    def as_dict(self) -> dict:
+        return {"refit_ms": self.refit_ms, "kernel_ms": self.kernel_ms, "sah_cost": self.sah_cost,
+                "sah_cost_built": self.sah_cost_built, "n_updates": int(self.n_updates),
+                "root_box": np.array(self.root_box[:], np.float32)}
+
+
 # every symbol the header declares (checked by tests/test_abi.py)
 EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "khp_set_scene", "khp_build_accel",
             "khp_render", "khp_read_framebuffer", "khp_trace_closest", "khp_trace_any", "khp_get_stats",
@@ -373,7 +385,8 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_get_lens", "khp_camera_rays_host", "khp_debug_camera_rays", "khp_hair_material",
             "khp_hair_eval_host", "khp_hair_sample_host", "khp_env_light_defaults", "khp_set_env_light",
             "khp_get_env_light", "khp_env_light_tables_host", "khp_env_light_sample_host", "khp_env_light_eval_host",
-            "khp_debug_env_light_tables", "khp_debug_env_light", "khp_kmath_host", "khp_debug_kmath"]
+            "khp_debug_env_light_tables", "khp_debug_env_light", "khp_kmath_host", "khp_debug_kmath",
+            "khp_update_geometry", "khp_update_geometry_device", "khp_get_refit_info", "khp_refit_host"]
 
 # khp_kmath_op (include/kirk_hip.h): the ops of khp_kmath_host / khp_debug_kmath, in enum order
 KMATH_OPS = ("mul", "add", "div", "sqrt", "rsqrt", "muladd", "floor", "f2i", "f2u", "i2f", "u2f", "u642f", "d2i2d",
@@ -550,6 +563,11 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
                                        P(c_float), P(c_float), P(c_float), P(c_float), P(c_float), P(c_float)]),
         "khp_host_build": (c_int, [P(SceneDesc), P(c_uint32), P(c_uint32), P(c_float), P(c_int32), P(c_int32),
                                    P(c_int32), P(c_float), P(c_float)]),
+        "khp_update_geometry": (c_int, [c_void_p, P(SceneDesc), P(RefitInfo)]),
+        "khp_update_geometry_device": (c_int, [c_void_p, P(SceneDesc), P(RefitInfo)]),
+        "khp_get_refit_info": (c_int, [c_void_p, P(RefitInfo)]),
+        "khp_refit_host": (c_int, [P(SceneDesc), c_uint32, P(c_int32), P(c_int32), P(c_int32), P(c_float),
+                                   P(c_float), P(c_float), P(ctypes.c_double)]),
     }
     lib.khp_abi_version.restype = c_int
     lib.khp_abi_version.argtypes = []
@@ -608,6 +626,28 @@ def host_build(scene) -> dict:
                                   ip(count), ip(ids), fptr(bounds), fptr(rec)), "khp_host_build")
     return {"boxes": boxes, "first": first, "count": count, "ids": ids, "bounds": bounds, "records": rec,
             "depth": dep.value}
+
+
+def refit_host(scene, bvh: dict) -> dict:
+    """khp_refit_host (host only): the topology of `bvh` (host_build's or read_bvh's dict: first,
+    count, ids) refitted to the moved `scene`: boxes, per-object bounds and records, sah_cost."""
+    lib = load_library()
+    d = scene.desc()
+    ip = lambda a: a.ctypes.data_as(POINTER(c_int32))
+    first = np.ascontiguousarray(bvh["first"], np.int32)
+    count = np.ascontiguousarray(bvh["count"], np.int32)
+    ids = np.ascontiguousarray(bvh["ids"], np.int32)
+    n, m = first.size, scene.n_objects
+    if count.size != n or ids.size != m:
+        raise ValueError("refit_host: first / count / ids do not fit the scene")
+    boxes = np.empty((n, 6), np.float32)
+    bounds = np.empty((m, 9), np.float32)
+    rec = np.empty((m, 16), np.float32)
+    cost = ctypes.c_double(0.0)
+    check(lib, lib.khp_refit_host(ctypes.byref(d), n, ip(first), ip(count), ip(ids), fptr(boxes), fptr(bounds),
+                                  fptr(rec), ctypes.byref(cost)), "khp_refit_host")
+    return {"boxes": boxes, "first": first, "count": count, "ids": ids, "bounds": bounds, "records": rec,
+            "sah_cost": cost.value}
 
 
 def gather_plan(width: int, height: int, tile: int, nranks: int, rank: int, root: int = 0):

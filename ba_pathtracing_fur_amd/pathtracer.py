@@ -178,6 +178,59 @@ class HipContext:
     def build_accel(self):
         N.check(self.lib, self.lib.khp_build_accel(self.ptr), "khp_build_accel")
 
+    def update_geometry(self, scene: SceneData) -> dict:
+        """khp_update_geometry: the built tree refitted in place to `scene`'s moved vertices (the same
+        object counts; only tri_v, tri_n, tri_frame, cone_base_r0 and cone_apex_r1 are read).  Returns
+        khp_refit_info as a dict.  Restart the accumulation: render the next frame with first_sample = 0."""
+        d = scene.desc()
+        info = N.RefitInfo()
+        N.check(self.lib, self.lib.khp_update_geometry(self.ptr, ctypes.byref(d), ctypes.byref(info)),
+                "khp_update_geometry")
+        self._scene = scene
+        return info.as_dict()
+
+    def update_geometry_device(self, scene: SceneData, cones=None) -> dict:
+        """khp_update_geometry_device: as update_geometry with the geometry copied to HBM first, or, with
+        cones=(base_r0, apex_r1, n) DeviceBuffers, those cones in place of the scene's own (mirrors
+        set_scene_device; a fourth element, the material, is ignored)."""
+        d = scene.desc()
+        keep = []
+
+        def dev(a):
+            b = DeviceBuffer.from_array(self, a)
+            keep.append(b)
+            return ctypes.cast(b.ptr, ctypes.POINTER(ctypes.c_float))
+
+        if len(scene.tri_v):
+            d.tri_v = dev(scene.tri_v)
+            d.tri_n = dev(scene.tri_n)
+            d.tri_frame = dev(scene.frames())
+        if cones is not None:
+            if len(scene.cone_base_r0):
+                raise ValueError("scene already has cones")
+            base, apex, nc = cones[:3]
+            d.n_cones = nc
+            d.cone_base_r0 = ctypes.cast(base.ptr, ctypes.POINTER(ctypes.c_float))
+            d.cone_apex_r1 = ctypes.cast(apex.ptr, ctypes.POINTER(ctypes.c_float))
+        elif len(scene.cone_base_r0):
+            d.cone_base_r0 = dev(scene.cone_base_r0)
+            d.cone_apex_r1 = dev(scene.cone_apex_r1)
+        info = N.RefitInfo()
+        try:
+            N.check(self.lib, self.lib.khp_update_geometry_device(self.ptr, ctypes.byref(d), ctypes.byref(info)),
+                    "khp_update_geometry_device")
+        finally:
+            for b in keep:
+                b.free()
+        self._scene = scene
+        return info.as_dict()
+
+    def refit_info(self) -> dict:
+        """khp_get_refit_info: the info of the last update_geometry (before the first: the built tree's)."""
+        info = N.RefitInfo()
+        N.check(self.lib, self.lib.khp_get_refit_info(self.ptr, ctypes.byref(info)), "khp_get_refit_info")
+        return info.as_dict()
+
     def params(self) -> dict:
         """khp_get_params: the context's scheduling parameters (khp_ctx_params)."""
         prm = N.CtxParams()
@@ -1246,6 +1299,9 @@ class TemporalAccumulator:
         acc = TemporalAccumulator(w, h, ctx)           # **params: khp_reproject_params fields
         shown = acc.push(cam, aov, colour)["colour"]   # every frame, moved camera or not
         acc.reset()                                    # after set_scene: the history is of another scene
+                                                       # (after update_geometry too: reset(), or keep it
+                                                       #  and let the object / depth tests reject what moved;
+                                                       #  either way render the next frame from first_sample = 0)
 
     The outputs alternate between two sets of buffers: what push() returns stays as it is until the
     push after the next.  The aov planes (and nothing else) are kept by reference as the next history's:
@@ -1259,7 +1315,8 @@ class TemporalAccumulator:
         self._sets, self._turn, self._hist = [None, None], 0, None
 
     def reset(self):
-        """Drop the history: the next push() starts one."""
+        """Drop the history: the next push() starts one.  HipContext.update_geometry does not do this, nor
+        restart the context's running mean, sample counts and moments: render with first_sample = 0."""
         self._hist = None
 
     @property

@@ -13,7 +13,7 @@ exact constants.
 from __future__ import annotations
 
 import ctypes
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -638,6 +638,53 @@ def sky_map(width: int, height: int, sun_dir=(0.3, 0.8, 0.5), sun_radiance=(4000
     sun.reshape(-1)[np.argmax(c)] = True
     img[sun] = np.asarray(sun_radiance, np.float64)
     return np.ascontiguousarray(img, np.float32)
+
+
+def bend_frame(sd: SceneData):
+    """The default (centre, radius) of bend(): the mean of the cone bases (of the triangle vertices in
+    a scene without cones) and the largest apex (vertex) distance from it, in float32."""
+    base = np.asarray(sd.cone_base_r0, np.float32).reshape(-1, 4)[:, :3]
+    far = np.asarray(sd.cone_apex_r1, np.float32).reshape(-1, 4)[:, :3]
+    if len(base) == 0:
+        base = far = np.asarray(sd.tri_v, np.float32).reshape(-1, 3)
+    centre = base.mean(axis=0, dtype=np.float32)
+    d = far - centre
+    return centre, np.float32(np.sqrt((d * d).sum(axis=1, dtype=np.float32).max()))
+
+
+def bend(sd: SceneData, amp: float, centre=None, radius=None) -> SceneData:
+    """A smooth deformation of every triangle vertex and cone base / apex p, in float32:
+    x += amp rho^2 sin(3 y), z += amp rho^2 cos(2 x_old), rho^2 = |p - centre|^2 / radius^2
+    (defaults: bend_frame).  A function of position alone, so vertices that coincide before
+    coincide after: chains and tubes stay connected.  Radii, normals, frames, materials and
+    everything else are shared with `sd` unchanged (for khp_update_geometry)."""
+    c0, r0 = bend_frame(sd)
+    c = np.asarray(c0 if centre is None else centre, np.float32)
+    r = np.float32(r0 if radius is None else radius)
+    a = np.float32(amp)
+
+    def move(p):
+        p = np.array(p, np.float32)
+        with np.errstate(all="ignore"):   # coordinates near FLT_MAX overflow here; the library refuses the result
+            return step(p)
+
+    def step(p):
+        d = p[..., :3] - c
+        rho2 = (d * d).sum(axis=-1, dtype=np.float32) / (r * r)
+        x_old = p[..., 0].copy()
+        p[..., 0] = x_old + a * rho2 * np.sin(np.float32(3.0) * p[..., 1])
+        p[..., 2] = p[..., 2] + a * rho2 * np.cos(np.float32(2.0) * x_old)
+        return p
+
+    out = replace(sd, tri_v=move(np.asarray(sd.tri_v, np.float32).reshape(-1, 3, 3)),
+                              cone_base_r0=move(np.asarray(sd.cone_base_r0, np.float32).reshape(-1, 4)),
+                              cone_apex_r1=move(np.asarray(sd.cone_apex_r1, np.float32).reshape(-1, 4)))
+    pts_in = np.concatenate([np.asarray(sd.tri_v, np.float32).reshape(-1, 3),
+                             np.asarray(sd.cone_apex_r1, np.float32).reshape(-1, 4)[:, :3]])
+    pts_out = np.concatenate([out.tri_v.reshape(-1, 3), out.cone_apex_r1[:, :3]])
+    _, first, inv = np.unique(pts_in.view(np.uint32), axis=0, return_index=True, return_inverse=True)
+    assert np.array_equal(pts_out.view(np.uint32), pts_out[first][inv.ravel()].view(np.uint32)), "bend: shared vertices split"
+    return out
 
 
 def rotation(axis, angle_rad: float) -> np.ndarray:

@@ -1410,6 +1410,62 @@ khp_status khp_camera_setup(const float position[3], const float look_at[3], con
  * Drops render-ahead work. */
 khp_status khp_set_camera(khp_ctx* ctx, const khp_camera* camera);
 
+/* Moved geometry without a rebuild (still ABI 17: symbols only).  khp_update_geometry
+ * re-flattens the objects of `moved` and refits the tree khp_build_accel left in HBM: the
+ * topology (children, leaf ranges, object order, slots, references) stays, every box,
+ * primitive record and base_d is recomputed, the two-level and top-of-tree records are
+ * remade.  Box union is min / max, so the refitted tree has one right answer per bit (up
+ * to the sign of a zero); khp_refit_host below computes the same on the host.
+ *
+ * Read from `moved`: n_tris, tri_v, tri_n, tri_frame, n_cones, cone_base_r0, cone_apex_r1.
+ * Materials, material indices, lights, camera, environment, textures, tri_uv, cone_models
+ * and cone_model stay as khp_set_scene left them.  khp_update_geometry_device takes the
+ * five arrays in device memory, as khp_set_scene_device does.
+ *
+ * KHP_EINVAL with the context unchanged: a null argument, n_tris or n_cones other than
+ * the built scene's, a missing array.  KHP_ENOTREADY: no tree yet.  KHP_EUNSUPPORTED: a
+ * KHP_CTX_HOST_BUILD context (its tree is not in HBM).  A NaN, an infinity or a float32
+ * overflow in the moved coordinates is KHP_EINVAL with khp_set_scene's messages, found
+ * after the object arrays were overwritten: the context is then left un-built
+ * (khp_render returns KHP_ENOTREADY) until the next successful khp_update_geometry, or
+ * khp_set_scene + khp_build_accel.  KHP_EDEVICE if a refitted box is not the union of
+ * its children's (never, for a tree this library built); that, or any other device error
+ * once the object arrays have started to change, leaves the context un-built in the same way.
+ *
+ * Like khp_set_camera the call completes frames in flight first and drops render-ahead
+ * work and parked paths of the old geometry.  The running mean, the sample counts and
+ * the moments are the caller's to restart: render the next frame with first_sample = 0.
+ *
+ * sah_cost = (sum over interior nodes of A(n) + sum over leaves of count(n) A(n)) / A(root),
+ * A the surface area of the float32 box evaluated in double: what the refit's looser
+ * boxes cost, next to sah_cost_built of the tree as khp_build_accel left it. */
+typedef struct {
+    double   refit_ms;        /* wall time of the call, transfers included                    */
+    double   kernel_ms;       /* HIP-event time of its kernels (three intervals, summed)      */
+    double   sah_cost;        /* of the tree as it now stands                                 */
+    double   sah_cost_built;  /* of the tree as khp_build_accel left it                       */
+    uint32_t n_updates;       /* successful updates since the last khp_build_accel            */
+    uint32_t reserved;
+    float    root_box[6];
+} khp_refit_info;
+
+khp_status khp_update_geometry(khp_ctx* ctx, const khp_scene* moved, khp_refit_info* info /* may be NULL */);
+khp_status khp_update_geometry_device(khp_ctx* ctx, const khp_scene* moved, khp_refit_info* info);
+/* The info of the last successful update; before the first one sah_cost == sah_cost_built,
+ * n_updates == 0 and the times are 0.  KHP_ENOTREADY without a tree, KHP_EUNSUPPORTED on a
+ * KHP_CTX_HOST_BUILD context. */
+khp_status khp_get_refit_info(khp_ctx* ctx, khp_refit_info* out);
+/* Host-only twin of the device refit (no device needed): flattens `moved` as khp_host_build
+ * does (a whole scene here: its materials and tables are checked as khp_set_scene checks
+ * them), then refits a topology given as khp_read_bvh / khp_host_build return it (preorder,
+ * count == 0 = interior, object_ids in leaf order).  node_boxes [n_nodes][6], obj_bounds
+ * [n_obj][9], records [n_obj][16] and sah_cost are outputs, each nullable.  KHP_EINVAL
+ * with nothing written: a null input, counts that do not describe a preorder tree of
+ * n_nodes nodes over the scene's objects, an object id out of range. */
+khp_status khp_refit_host(const khp_scene* moved, uint32_t n_nodes, const int32_t* node_first,
+                          const int32_t* node_count, const int32_t* object_ids,
+                          float* node_boxes, float* obj_bounds, float* records, double* sah_cost);
+
 /* Fur fibers -> cone frusta exactly as CPU_Scene::flattenNode does with
  * m_fiberAsCylinder (CPU_Scene.cpp:121-144): base pulled back by 0.8 % of the
  * segment, base radius shrunk 5 % (segment index <= 3) or 10 %.
