@@ -178,6 +178,7 @@ __global__ __launch_bounds__(256) void k_aov_reduce(AovCols R, AovOut O, const u
 }
 
 // ---- host side ---------------------------------------------------------------------------
+template <size_t I> struct AovK { static constexpr auto k = k_aov_trace<AOV_TABLE[I].tex, AOV_TABLE[I].lens>; };
 // The call's own device state (khp_ctx::aov): nothing of it is shared with the
 // renderer, whose path sets, pixel list and spill columns may be in use by
 // frames in flight.
@@ -223,13 +224,10 @@ extern "C" khp_status khp_render_aov(khp_ctx* c, const khp_render_params* p, con
     }
     if (!c->aov) c->aov = std::make_shared<AovState>();
     AovState& A = *c->aov;
-    const bool tex = c->S.textured != 0;
-    if (!A.grid[tex]) {
-        int nb = 0;
-        if (tex) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_aov_trace<true>, TRAV_BLOCK, AOV_LDS_BYTES));
-        else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_aov_trace<false>, TRAV_BLOCK, AOV_LDS_BYTES));
-        A.grid[tex] = std::max(1, nb) * c->n_cu;
-    }
+    const AovVariant va = select_aov(variant_facts(c));   // khp_set_lens: the lens twins (the same launch bounds and grid)
+    const bool tex = va.tex;
+    if (!A.grid[tex])   // sized from the instance without the lens, whichever runs
+        KHPCHK(variant_grid<AovK>(c, AOV_TABLE, {tex, false}, TRAV_BLOCK, AOV_LDS_BYTES, A.grid[tex]));
     // chunks of whole pixels under the context's chunk_paths rule (decided before the scratch takes memory)
     const size_t cap_paths = std::max<size_t>(4096, chunk_paths(c));
     KHPCHK(aov_pixels(c, A, p));
@@ -286,7 +284,6 @@ extern "C" khp_status khp_render_aov(khp_ctx* c, const khp_render_params* p, con
     Wv.pix_major = 1;
     Wv.fsample0[0] = p->first_sample;
     const SpillArea sp{A.spill.as<int4>(), (uint32_t)grid * TRAV_BLOCK};
-    const bool lens = c->S.lens.radius > 0.0f;   // khp_set_lens: the lens twins (the same launch bounds and grid)
     for (uint32_t p_off = 0; p_off < P_all; p_off += P_chunk) {
         const uint32_t P = std::min(P_chunk, P_all - p_off), n = P * spp;
         Wv.P = P;
@@ -294,10 +291,7 @@ extern "C" khp_status khp_render_aov(khp_ctx* c, const khp_render_params* p, con
         Wv.cap = n;
         HIPCHK(hipMemsetAsync(A.cnt.p, 0, sizeof(Counters), c->stream));
         hipLaunchKernelGGL(k_start, dim3(1), dim3(1), 0, c->stream, Wv.cnt, n);
-        if (lens && tex) hipLaunchKernelGGL((k_aov_trace<true, true>), dim3(grid), dim3(TRAV_BLOCK), AOV_LDS_BYTES, c->stream, c->S, Wv, sp, R);
-        else if (lens) hipLaunchKernelGGL((k_aov_trace<false, true>), dim3(grid), dim3(TRAV_BLOCK), AOV_LDS_BYTES, c->stream, c->S, Wv, sp, R);
-        else if (tex) hipLaunchKernelGGL(k_aov_trace<true>, dim3(grid), dim3(TRAV_BLOCK), AOV_LDS_BYTES, c->stream, c->S, Wv, sp, R);
-        else hipLaunchKernelGGL(k_aov_trace<false>, dim3(grid), dim3(TRAV_BLOCK), AOV_LDS_BYTES, c->stream, c->S, Wv, sp, R);
+        KHPCHK(launch_variant<AovK>(AOV_TABLE, va, grid, TRAV_BLOCK, AOV_LDS_BYTES, c->stream, c->S, Wv, sp, R));
         hipLaunchKernelGGL(k_aov_reduce, dim3((P + 255) / 256), dim3(256), 0, c->stream, R, O, Wv.pix, p_off, P, spp);
         HIPCHK(hipGetLastError());
     }

@@ -12,6 +12,7 @@
 #include "hair_pb.h"
 #include "env_light.h"
 #include "scene.h"
+#include "variant.h"   // the KINDS_* sets and the tables of compiled kernel instances
 
 namespace khp {
 
@@ -527,10 +528,7 @@ __device__ __forceinline__ v3 hair_r(const ShadeCtx& s, v3 in, v3 n, float sampl
 
 namespace khp {
 
-// A spare bit of the KINDS sets below: the instance traces Marschner's TT and TRT
-// paths (khp_set_hair_lobes).  The all-ones default of KINDS predates the bit and
-// means every BSDF kind with the R lobe only.
-constexpr uint32_t KINDS_LOBES = 1u << 31;
+// KINDS_LOBES (variant.h): the instance traces Marschner's TT and TRT paths; never read off the all-ones default.
 template <uint32_t KINDS>
 constexpr bool kinds_lobes = KINDS != 0xFFFFFFFFu && (KINDS & KINDS_LOBES) != 0u;
 

@@ -592,33 +592,6 @@ __global__ __launch_bounds__(TRAV_BLOCK, WIDE ? EXT_WAVES_W : CAM ? CAM_WAVES : 
                     &Wv.cnt->lanes_busy, &Wv.cnt->spills);
 }
 
-// Host-side launch of the k_extend instance for (stats, camera rays in place, wide records).
-// The camera-bounce instances have a lens twin each (khp_set_lens: S.lens.radius > 0).
-static void launch_extend(bool stats, bool cam, bool wide, int grid, hipStream_t s, const DevScene& S, const Wave& W,
-                          int cur, SpillArea sp, bool top = false) {
-    const dim3 g(grid), b(TRAV_BLOCK);
-    const bool lens = cam && S.lens.radius > 0.0f;
-    if (top && !stats && !wide && S.top) {   // the top records in LDS (lds_nodes)
-        if (lens) hipLaunchKernelGGL((k_extend<false, true, false, true, true>), g, b, CAM_LDS_BYTES + TOP_LDS_BYTES, s, S, W, cur, sp);
-        else if (cam) hipLaunchKernelGGL((k_extend<false, true, false, true>), g, b, CAM_LDS_BYTES + TOP_LDS_BYTES, s, S, W, cur, sp);
-        else hipLaunchKernelGGL((k_extend<false, false, false, true>), g, b, EXT_LDS_BYTES + TOP_LDS_BYTES, s, S, W, cur, sp);
-        return;
-    }
-#define KHP_EXT(ST, CA, WI)                                                                                        \
-    do {                                                                                                           \
-        if (CA && lens) hipLaunchKernelGGL((k_extend<ST, CA, WI, false, CA>), g, b, CAM_LDS_BYTES, s, S, W, cur, sp); \
-        else hipLaunchKernelGGL((k_extend<ST, CA, WI>), g, b, CA ? CAM_LDS_BYTES : EXT_LDS_BYTES, s, S, W, cur, sp); \
-    } while (0)
-    if (wide) {
-        if (stats) { if (cam) KHP_EXT(true, true, true); else KHP_EXT(true, false, true); }
-        else { if (cam) KHP_EXT(false, true, true); else KHP_EXT(false, false, true); }
-    } else {
-        if (stats) { if (cam) KHP_EXT(true, true, false); else KHP_EXT(true, false, false); }
-        else { if (cam) KHP_EXT(false, true, false); else KHP_EXT(false, false, false); }
-    }
-#undef KHP_EXT
-}
-
 // ---- light-path variant (khp_bdpt_params, ABI 7; lightpath.h) ----------------------------
 // The surface at a closest hit: normal, hair frame and material (k_shade's
 // calcNormal / calcTcoord code; Cylinder.cpp:230-260, Triangle.cpp:244-254).
@@ -1089,8 +1062,9 @@ __device__ __forceinline__ void block_alloc2(bool p0, bool p1, uint32_t* c0, uin
 #ifndef KHP_SHADE_BLOCK_PLAIN
 #define KHP_SHADE_BLOCK_PLAIN 1024
 #endif
+constexpr uint32_t shade_block(bool tex, bool bd) { return (!tex && !bd) ? KHP_SHADE_BLOCK_PLAIN : KHP_SHADE_BLOCK; }
 template <bool TEX, bool BD>
-constexpr uint32_t shade_block() { return (!TEX && !BD) ? KHP_SHADE_BLOCK_PLAIN : KHP_SHADE_BLOCK; }
+constexpr uint32_t shade_block() { return shade_block(TEX, BD); }
 // Four outputs (next-bounce rays and shadow rays, each front or back): a lane
 // sets at most one of p0/p1 and one of p2/p3; i01 / i23 is its index in the
 // queue it was counted in.
@@ -1536,59 +1510,6 @@ __global__ __launch_bounds__((shade_block<TEX, BD>()), KHP_SHADE_WAVES) void k_s
     }
 }
 
-// BSDF kind sets k_shade and k_path are instantiated for: every kind, or the fur scenes'
-// (Lambert reflection + Marschner hair: configs 1-3 and the metric row), where
-// the other kinds' code and registers are compiled out.
-constexpr uint32_t KINDS_ALL = 0x7FFu;   // KIRK's eleven kinds
-// Scenes with a kind-11 material (hair_pb.h) take one covering set: the eleven and ChiangHairBSDF.
-constexpr uint32_t KINDS_ALL_HAIR = (1u << KHP_BSDF_COUNT) - 1u;
-constexpr uint32_t KINDS_FUR_HAIR = (1u << KHP_BSDF_LAMBERTIAN_REFLECTION) | (1u << KHP_BSDF_CHIANG_HAIR);
-static_assert(KINDS_ALL_HAIR == 0xFFFu, "the covering set of scenes with kind 11");
-constexpr uint32_t KINDS_FUR = (1u << KHP_BSDF_LAMBERTIAN_REFLECTION) | (1u << KHP_BSDF_MARSCHNER_HAIR);
-// Host-side launch of the k_shade instance for (textured, light-path variant, fur-only scene, TT / TRT lobes);
-// grid_bd is the light-path instances' grid.  The lobe instances (never with the light-path variant) name their
-// kinds with KINDS_ALL; the others that keep every kind take k_shade's defaulted KINDS, a different instance.
-static void launch_shade(bool tex, bool bd, bool fur, bool lobes, bool hair, int grid, int grid_bd, hipStream_t s,
-                         const DevScene& S, const Wave& W, int cur, uint32_t bounce) {
-    constexpr uint32_t DEFAULTED = 0xFFFFFFFFu;
-    // khp_set_lens: the lens twin, for the one launch that recomputes camera rays (never with the light-path variant)
-    const bool lens = !bd && bounce == 0u && W.cam0 != 0u && S.lens.radius > 0.0f;
-#define KHP_SHADE(TEX, BD, K)                                                                                          \
-    do {                                                                                                               \
-        if (!BD && lens)                                                                                               \
-            hipLaunchKernelGGL((k_shade<TEX, BD, K, !BD>), dim3(grid), dim3(shade_block<TEX, BD>()), 0, s, S, W, cur, bounce); \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_shade<TEX, BD, K>), dim3(BD ? grid_bd : grid), dim3(shade_block<TEX, BD>()), 0, s, S, W, \
-                               cur, bounce);                                                                           \
-    } while (0)
-    if (S.envl) {   // khp_set_env_light: the covering kind set with the light compiled in (never with bd or lobes)
-#define KHP_SHADE_ENV(TEX)                                                                                             \
-    do {                                                                                                               \
-        if (lens)                                                                                                      \
-            hipLaunchKernelGGL((k_shade<TEX, false, KINDS_ALL_HAIR, true, true>), dim3(grid),                          \
-                               dim3(shade_block<TEX, false>()), 0, s, S, W, cur, bounce);                              \
-        else                                                                                                           \
-            hipLaunchKernelGGL((k_shade<TEX, false, KINDS_ALL_HAIR, false, true>), dim3(grid),                         \
-                               dim3(shade_block<TEX, false>()), 0, s, S, W, cur, bounce);                              \
-    } while (0)
-        if (tex) KHP_SHADE_ENV(true);
-        else KHP_SHADE_ENV(false);
-#undef KHP_SHADE_ENV
-        return;
-    }
-    if (hair && tex) KHP_SHADE(true, false, KINDS_ALL_HAIR);   // ChiangHairBSDF compiled in (never with bd or lobes)
-    else if (hair) KHP_SHADE(false, false, KINDS_ALL_HAIR);
-    else if (lobes && tex) KHP_SHADE(true, false, KINDS_ALL | KINDS_LOBES);   // TT / TRT compiled in
-    else if (lobes && fur) KHP_SHADE(false, false, KINDS_FUR | KINDS_LOBES);
-    else if (lobes) KHP_SHADE(false, false, KINDS_ALL | KINDS_LOBES);
-    else if (tex && bd) KHP_SHADE(true, true, DEFAULTED);
-    else if (tex) KHP_SHADE(true, false, DEFAULTED);
-    else if (bd) KHP_SHADE(false, true, DEFAULTED);
-    else if (fur) KHP_SHADE(false, false, KINDS_FUR);   // fur scenes: the other BSDF kinds compiled out
-    else KHP_SHADE(false, false, DEFAULTED);
-#undef KHP_SHADE
-}
-
 // ---- shadow: BVH::isIntersection (k_shadow), then the light occlusion loop and
 //      the deferred colour add (k_shadow_finish, SimpleShader.h:131-148) ---------------
 // k_shadow_finish: one shadow record per lane, streaming; kept out of the
@@ -1740,23 +1661,6 @@ __global__ __launch_bounds__(TRAV_BLOCK, TRAV_WAVES) void k_shadow(DevScene S, W
     if (STATS)
         flush_stats(st, stk, wit, wbusy, &Wv.cnt->sh_node_visits, &Wv.cnt->sh_prim_tests, &Wv.cnt->sh_pruned,
                     &Wv.cnt->sh_iters, &Wv.cnt->sh_lanes_busy, &Wv.cnt->spills);
-}
-
-// Host-side launch of the k_shadow instance for (stats, wide records).
-static void launch_shadow(bool stats, bool wide, int grid, hipStream_t s, const DevScene& S, const Wave& W, SpillArea sp,
-                          bool top = false) {
-    const dim3 g(grid), b(TRAV_BLOCK);
-    if (top && !stats && !wide && S.top) {
-        hipLaunchKernelGGL((k_shadow<false, false, true>), g, b, LDS_BYTES + TOP_LDS_BYTES, s, S, W, sp);
-        return;
-    }
-    if (wide) {
-        if (stats) hipLaunchKernelGGL((k_shadow<true, true>), g, b, LDS_BYTES, s, S, W, sp);
-        else hipLaunchKernelGGL((k_shadow<false, true>), g, b, LDS_BYTES, s, S, W, sp);
-    } else {
-        if (stats) hipLaunchKernelGGL((k_shadow<true, false>), g, b, LDS_BYTES, s, S, W, sp);
-        else hipLaunchKernelGGL((k_shadow<false, false>), g, b, LDS_BYTES, s, S, W, sp);
-    }
 }
 
 // ---- path kernel: every bounce of a path in one persistent launch (khp_ctx_params.path_kernel) ----
@@ -2283,53 +2187,6 @@ __global__ __launch_bounds__(TRAV_BLOCK, PATH_WAVES) void k_path(DevScene S, Wav
 }
 
 constexpr size_t PATH_LDS = PATH_LDS_BYTES;
-template <bool TEX, bool WIDE, uint32_t K, bool ENV = false>
-static void launch_path_k(int grid, hipStream_t s, const DevScene& S, const Wave& W, SpillArea sp, const PathLanes& L,
-                          const Ahead& A, bool qs) {
-    if constexpr (ENV) {   // khp_set_env_light: the twins of the launches below
-        const dim3 g(grid), b(TRAV_BLOCK);
-        if (qs) hipLaunchKernelGGL((k_path<TEX, WIDE, K, false, true, false, true>), g, b, PATH_LDS, s, S, W, sp, L, A);
-        else if (S.lens.radius > 0.0f && A.on) hipLaunchKernelGGL((k_path<TEX, WIDE, K, true, false, true, true>), g, b, PATH_LDS, s, S, W, sp, L, A);
-        else if (S.lens.radius > 0.0f) hipLaunchKernelGGL((k_path<TEX, WIDE, K, false, false, true, true>), g, b, PATH_LDS, s, S, W, sp, L, A);
-        else if (A.on) hipLaunchKernelGGL((k_path<TEX, WIDE, K, true, false, false, true>), g, b, PATH_LDS, s, S, W, sp, L, A);
-        else hipLaunchKernelGGL((k_path<TEX, WIDE, K, false, false, false, true>), g, b, PATH_LDS, s, S, W, sp, L, A);
-        return;
-    }
-    if (qs) {
-        hipLaunchKernelGGL((k_path<TEX, WIDE, K, false, true>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
-        return;
-    }
-    if (S.lens.radius > 0.0f) {   // khp_set_lens: the lens twins
-        if (A.on) hipLaunchKernelGGL((k_path<TEX, WIDE, K, true, false, true>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
-        else hipLaunchKernelGGL((k_path<TEX, WIDE, K, false, false, true>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
-        return;
-    }
-    if (A.on) hipLaunchKernelGGL((k_path<TEX, WIDE, K, true>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
-    else hipLaunchKernelGGL((k_path<TEX, WIDE, K, false>), dim3(grid), dim3(TRAV_BLOCK), PATH_LDS, s, S, W, sp, L, A);
-}
-// lobes: the instances with Marschner's TT / TRT paths compiled in (khp_set_hair_lobes)
-static void launch_path(bool tex, bool wide, bool fur, bool lobes, bool hair, int grid, hipStream_t s, const DevScene& S,
-                        const Wave& W, SpillArea sp, const PathLanes& L, const Ahead& A, bool qs = false) {
-#define KHP_PATH(TEX, K)                                                    \
-    (wide ? launch_path_k<TEX, true, K>(grid, s, S, W, sp, L, A, qs)        \
-          : launch_path_k<TEX, false, K>(grid, s, S, W, sp, L, A, qs))
-    if (S.envl) {   // khp_set_env_light: the covering kind set with the light compiled in
-        if (tex) (wide ? launch_path_k<true, true, KINDS_ALL_HAIR, true>(grid, s, S, W, sp, L, A, qs)
-                       : launch_path_k<true, false, KINDS_ALL_HAIR, true>(grid, s, S, W, sp, L, A, qs));
-        else (wide ? launch_path_k<false, true, KINDS_ALL_HAIR, true>(grid, s, S, W, sp, L, A, qs)
-                   : launch_path_k<false, false, KINDS_ALL_HAIR, true>(grid, s, S, W, sp, L, A, qs));
-        return;
-    }
-    if (hair && tex) KHP_PATH(true, KINDS_ALL_HAIR);   // the ladder of launch_shade
-    else if (hair) KHP_PATH(false, KINDS_ALL_HAIR);
-    else if (lobes && tex) KHP_PATH(true, KINDS_ALL | KINDS_LOBES);
-    else if (lobes && fur) KHP_PATH(false, KINDS_FUR | KINDS_LOBES);
-    else if (lobes) KHP_PATH(false, KINDS_ALL | KINDS_LOBES);
-    else if (tex) KHP_PATH(true, KINDS_ALL);
-    else if (fur) KHP_PATH(false, KINDS_FUR);
-    else KHP_PATH(false, KINDS_ALL);
-#undef KHP_PATH
-}
 
 // ---- accumulate: PathTracer::drawTexture running mean (CPU_PathTracer.cpp:61-90) -------
 // The accumulate kernels -- two here, k_accumulate_m and k_accumulate_all_m in moments_dev.h,
@@ -2952,6 +2809,67 @@ static bool render_stats(const khp_ctx* c, const khp_render_params* p) {
     return (c->flags & KHP_CTX_STATS) != 0 || (p->flags & KHP_RENDER_STATS) != 0;
 }
 static bool render_async(const khp_render_params* p) { return (p->flags & KHP_RENDER_ASYNC) != 0; }
+
+// ---- kernel instances by table (variant.h) ------------------------------------------------
+// What the selectors of variant.h choose from, read off the context: once per batch (plan_batch), and
+// by the ray queries and khp_render_aov.
+static VariantFacts variant_facts(const khp_ctx* c) {
+    return {c->S.textured != 0, fur_only(c), c->S.hair_lobes != HAIR_LOBE_R,
+            (c->bsdf_kinds & (1u << KHP_BSDF_CHIANG_HAIR)) != 0u, c->S.envl != nullptr, c->S.lens.radius > 0.0f,
+            light_paths_on(c)};
+}
+// Row I of a family's table as its kernel.  Only these name the kernels' template arguments, so the
+// instances compiled are the tables' rows.
+template <size_t I> struct ShadeK {
+    static constexpr ShadeVariant v = SHADE_TABLE[I];
+    static constexpr auto k = k_shade<v.tex, v.bd, v.kinds, v.lens, v.env>;
+};
+template <size_t I> struct PathK {
+    static constexpr PathVariant v = PATH_TABLE[I];
+    static constexpr auto k = k_path<v.tex, v.wide, v.kinds, v.ra, v.qs, v.lens, v.env>;
+};
+template <size_t I> struct ExtendK {
+    static constexpr ExtendVariant v = EXTEND_TABLE[I];
+    static constexpr auto k = k_extend<v.stats, v.cam, v.wide, v.top, v.lens>;
+};
+template <size_t I> struct ShadowK {
+    static constexpr ShadowVariant v = SHADOW_TABLE[I];
+    static constexpr auto k = k_shadow<v.stats, v.wide, v.top>;
+};
+template <size_t I> struct GenerateK { static constexpr auto k = k_generate<GENERATE_TABLE[I].lens>; };
+template <size_t I> struct ShadowFinishK { static constexpr auto k = k_shadow_finish<SHADOW_FINISH_TABLE[I].bd>; };
+// The kernel of the row equal to `want`; null: the table has no such row.
+template <template <size_t> class K, class V, size_t N, size_t... I>
+static auto variant_kernel(const std::array<V, N>& table, const V& want, std::index_sequence<I...>) {
+    std::remove_const_t<decltype(K<0>::k)> k = nullptr;
+    (void)((table[I].args() == want.args() && (k = K<I>::k, true)) || ...);
+    return k;
+}
+template <template <size_t> class K, class V, size_t N, class... A>
+static khp_status launch_variant(const std::array<V, N>& table, const V& want, int grid, uint32_t block, size_t lds,
+                                 hipStream_t s, const A&... a) {
+    const auto k = variant_kernel<K>(table, want, std::make_index_sequence<N>{});
+    if (!k) return fail(KHP_EINVAL, "internal: no such instance");
+    hipLaunchKernelGGL(k, dim3(grid), dim3(block), lds, s, a...);
+    return KHP_OK;
+}
+// The resident grid of an instance: its blocks per CU x the CUs.  khp_build_accel sizes several grids
+// from an instance other than the one a scene with ChiangHairBSDF, the lobes, the lens or the environment
+// light later launches on them: the grids are sized once, from the plain instances.
+template <template <size_t> class K, class V, size_t N>
+static khp_status variant_grid(const khp_ctx* c, const std::array<V, N>& table, const V& want, uint32_t block,
+                               size_t lds, int& grid) {
+    const auto k = variant_kernel<K>(table, want, std::make_index_sequence<N>{});
+    if (!k) return fail(KHP_EINVAL, "internal: no such instance");
+    int nb = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, (int)block, lds));
+    grid = std::max(1, nb) * c->n_cu;
+    return KHP_OK;
+}
+constexpr size_t extend_lds(const ExtendVariant& v) {
+    return (v.cam ? CAM_LDS_BYTES : EXT_LDS_BYTES) + (v.top ? TOP_LDS_BYTES : 0);
+}
+constexpr size_t shadow_lds(const ShadowVariant& v) { return LDS_BYTES + (v.top ? TOP_LDS_BYTES : 0); }
 
 static khp_status drain(khp_ctx* c);
 static void comm_release(khp_ctx* c);
@@ -3676,58 +3594,30 @@ extern "C" khp_status khp_build_accel(khp_ctx* c) {
     c->st.max_leaf_size = hs.max_leaf;
     c->st.device_bytes = c->prims.bytes + c->aux.bytes + c->trinrm.bytes + c->trifrm.bytes + c->nodes.bytes + c->wide.bytes + c->mats.bytes +
                          c->lights.bytes;
-    // persistent grid sizes
-    int nb = 0;
-    if (c->flags & KHP_CTX_STATS)
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_extend<true>, TRAV_BLOCK, EXT_LDS_BYTES));
-    else
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_extend<false>, TRAV_BLOCK, EXT_LDS_BYTES));
-    c->grid_ext = std::max(1, nb) * c->n_cu;
-    nb = 0;
-    if (c->flags & KHP_CTX_STATS)
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_extend<true, false, true>, TRAV_BLOCK, EXT_LDS_BYTES));
-    else
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_extend<false, false, true>, TRAV_BLOCK, EXT_LDS_BYTES));
-    c->grid_ext_w = std::max(1, nb) * c->n_cu;
-    nb = 0;
-    if (c->flags & KHP_CTX_STATS)
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_extend<true, true>, TRAV_BLOCK, CAM_LDS_BYTES));
-    else
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_extend<false, true>, TRAV_BLOCK, CAM_LDS_BYTES));
-    c->grid_ext_cam = std::max(1, nb) * c->n_cu;
+    // persistent grid sizes, each from a named instance (variant_grid)
+    const bool st = (c->flags & KHP_CTX_STATS) != 0, tex = S.textured != 0;
+    KHPCHK(variant_grid<ExtendK>(c, EXTEND_TABLE, {st, false, false, false, false}, TRAV_BLOCK, EXT_LDS_BYTES, c->grid_ext));
+    KHPCHK(variant_grid<ExtendK>(c, EXTEND_TABLE, {st, false, true, false, false}, TRAV_BLOCK, EXT_LDS_BYTES, c->grid_ext_w));
+    KHPCHK(variant_grid<ExtendK>(c, EXTEND_TABLE, {st, true, false, false, false}, TRAV_BLOCK, CAM_LDS_BYTES, c->grid_ext_cam));
     c->grid_ext_max = std::max(c->grid_ext, std::max(c->grid_ext_w, c->grid_ext_cam));
-    nb = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_shadow<false>, TRAV_BLOCK, LDS_BYTES));
-    c->grid_sh = std::max(1, nb) * c->n_cu;
-    nb = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_shadow<false, true>, TRAV_BLOCK, LDS_BYTES));
-    c->grid_sh_w = std::min(c->grid_sh, std::max(1, nb) * c->n_cu);  // the spill columns are sized by grid_sh
+    KHPCHK(variant_grid<ShadowK>(c, SHADOW_TABLE, {false, false, false}, TRAV_BLOCK, LDS_BYTES, c->grid_sh));
+    KHPCHK(variant_grid<ShadowK>(c, SHADOW_TABLE, {false, true, false}, TRAV_BLOCK, LDS_BYTES, c->grid_sh_w));
+    c->grid_sh_w = std::min(c->grid_sh, c->grid_sh_w);  // the spill columns are sized by grid_sh
     c->bsdf_kinds = 0;   // the kinds the materials use: fur scenes run kernels with the others compiled out
     for (const khp_material& m : hs.mats)
         c->bsdf_kinds |= (m.bsdf >= 0 && m.bsdf < KHP_BSDF_COUNT) ? (1u << m.bsdf) : KINDS_ALL_HAIR;
-    nb = 0;
-    if (S.textured) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_shade<true, false>), shade_block<true, false>(), 0));
-    else if (fur_only(c))
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_shade<false, false, KINDS_FUR>), shade_block<false, false>(), 0));
-    else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_shade<false, false>), shade_block<false, false>(), 0));
-    c->grid_shade = std::max(1, nb) * c->n_cu;
-    nb = 0;
-    if (S.textured) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_shade<true, true>), shade_block<true, true>(), 0));
-    else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_shade<false, true>), shade_block<false, true>(), 0));
-    c->grid_shade_bd = std::max(1, nb) * c->n_cu;
+    const ShadeVariant plain{tex, false, !tex && fur_only(c) ? KINDS_FUR : KINDS_DEFAULT, false, false};
+    KHPCHK(variant_grid<ShadeK>(c, SHADE_TABLE, plain, shade_block(tex, false), 0, c->grid_shade));
+    KHPCHK(variant_grid<ShadeK>(c, SHADE_TABLE, {tex, true, KINDS_DEFAULT, false, false}, shade_block(tex, true), 0,
+                                c->grid_shade_bd));
     // k_shadow_finish streams shadow records in 256-thread blocks: its own occupancy grid
     // (k_shade's 512-thread grid gave it 0.4x the threads: 0.333 vs 0.314 ms per frame)
-    nb = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_shadow_finish<false>), 256, 0));
-    c->grid_fin = std::max(1, nb) * c->n_cu;
-    nb = 0;
-    if (S.textured) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_path<true, false, KINDS_ALL, true>), TRAV_BLOCK, PATH_LDS));
-    else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_path<false, false, KINDS_ALL, true>), TRAV_BLOCK, PATH_LDS));
-    c->grid_path = std::max(1, nb) * c->n_cu;
-    nb = 0;
-    if (S.textured) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_path<true, true, KINDS_ALL, true>), TRAV_BLOCK, PATH_LDS));
-    else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (k_path<false, true, KINDS_ALL, true>), TRAV_BLOCK, PATH_LDS));
-    c->grid_path_w = std::min(c->grid_path, std::max(1, nb) * c->n_cu);   // the columns are sized by grid_path
+    KHPCHK(variant_grid<ShadowFinishK>(c, SHADOW_FINISH_TABLE, {false}, 256, 0, c->grid_fin));
+    KHPCHK(variant_grid<PathK>(c, PATH_TABLE, {tex, false, KINDS_ALL, true, false, false, false}, TRAV_BLOCK, PATH_LDS,
+                               c->grid_path));
+    KHPCHK(variant_grid<PathK>(c, PATH_TABLE, {tex, true, KINDS_ALL, true, false, false, false}, TRAV_BLOCK, PATH_LDS,
+                               c->grid_path_w));
+    c->grid_path_w = std::min(c->grid_path, c->grid_path_w);   // the columns are sized by grid_path
     c->built = true;
     c->can_refit = !host_build;
     ++c->gen;
@@ -4251,8 +4141,7 @@ struct BatchPlan {
     bool use_path, path_wide;    // the path kernel; on the two-level records
     uint32_t hyb_from, rs_from;  // k_path takes over at this bounce (hybrid batches); ray sorting from this one (0: off)
     bool hyb_wide, ahead;        // ahead: render-ahead in the path kernel
-    bool lobes_on, fur_only;     // khp_set_hair_lobes: the KINDS_LOBES instances; the KINDS_FUR instances
-    bool hair;                   // a ChiangHairBSDF material in the scene: the KINDS_ALL_HAIR instances
+    VariantFacts vf;             // what the kernel instances are chosen from (variant.h)
     bool overlap;                // the shadow stage on its own stream
     int grid_ext, grid_ext_w, grid_ext_cam, grid_sh, grid_sh_w, grid_path;   // this batch's share of the resident grids
 };
@@ -4357,9 +4246,7 @@ static khp_status plan_batch(khp_ctx* c, const khp_render_params* p, const std::
     pl.hyb_from = (path_ok && !pl.use_path && c->prm.path_from > 0 && c->prm.path_from < p->depth) ? c->prm.path_from : 0u;
     pl.hyb_wide = pl.hyb_from > 0 && c->S.wide != nullptr && pl.hyb_from >= c->prm.wide_from;
     pl.grid_path = std::max(1, ((pl.path_wide || pl.hyb_wide) ? c->grid_path_w : c->grid_path) / G);
-    pl.lobes_on = c->S.hair_lobes != HAIR_LOBE_R;
-    pl.fur_only = fur_only(c);
-    pl.hair = (c->bsdf_kinds & (1u << KHP_BSDF_CHIANG_HAIR)) != 0u;
+    pl.vf = variant_facts(c);
     // Two streams: A runs generate / extend / shade / accumulate, B runs the
     // shadow stage (k_shadow + k_shadow_finish) of bounce b while A already
     // traverses bounce b+1, so each persistent kernel's tail fills with the
@@ -4548,8 +4435,10 @@ static khp_status enqueue_bounce(khp_ctx* c, const BatchPlan& pl, const khp_rend
     timed(c, f, T_EXTEND, true, sA);
     const bool cam = b == 0 && Wv.cam0;
     const bool wide = c->S.wide != nullptr && b >= c->prm.wide_from;
-    launch_extend(pl.stats, cam, wide, wide ? pl.grid_ext_w : cam ? pl.grid_ext_cam : pl.grid_ext, sA, c->S, Wb, cur,
-                  B.sp_ext, c->prm.lds_nodes != 0);
+    const bool top = c->prm.lds_nodes != 0, has_top = c->S.top != nullptr;
+    const ExtendVariant ve = select_extend(pl.vf, pl.stats, cam, wide, top, has_top);
+    KHPCHK(launch_variant<ExtendK>(EXTEND_TABLE, ve, wide ? pl.grid_ext_w : cam ? pl.grid_ext_cam : pl.grid_ext, TRAV_BLOCK,
+                                   extend_lds(ve), sA, c->S, Wb, cur, B.sp_ext));
     timed(c, f, T_EXTEND, false, sA);
     if (k.done_b && sB != sA) HIPCHK(hipStreamWaitEvent(sA, k.done_b, 0));
     timed(c, f, T_SHADE, true, sA);
@@ -4558,8 +4447,9 @@ static khp_status enqueue_bounce(khp_ctx* c, const BatchPlan& pl, const khp_rend
         hipLaunchKernelGGL(k_hit_class, dim3(c->grid_shade), dim3(256), 0, sA, c->S, Wb, cur);
         hipLaunchKernelGGL(k_hit_scatter, dim3(c->grid_shade), dim3(256), 0, sA, Wb, cur);
     }
-    launch_shade(c->S.textured != 0, pl.bdm, pl.fur_only, pl.lobes_on, pl.hair, c->grid_shade, c->grid_shade_bd, sA, c->S, Wb,
-                 cur, b);
+    const ShadeVariant vs = select_shade(pl.vf, b, Wb.cam0 != 0u);
+    KHPCHK(launch_variant<ShadeK>(SHADE_TABLE, vs, vs.bd ? c->grid_shade_bd : c->grid_shade, shade_block(vs.tex, vs.bd), 0,
+                                  sA, c->S, Wb, cur, b));
     timed(c, f, T_SHADE, false, sA);
     k.sorted = pl.rs_from > 0 && b + 1 >= pl.rs_from && b + 1 < p->depth;
     if (k.sorted) KHPCHK(regroup_next_queue(c, B, cur));   // before the shadow stage forks: alone on the chip it takes
@@ -4577,11 +4467,13 @@ static khp_status enqueue_bounce(khp_ctx* c, const BatchPlan& pl, const khp_rend
     if (dump) KHPCHK(dump_shadow_queue(c, Wb, sA));
     timed(c, f, T_SHADOW, true, sB);
     const bool wide_sh = c->S.wide != nullptr && b >= std::max(c->prm.wide_from, (uint32_t)KHP_WIDE_SH_FROM);
-    launch_shadow(pl.stats, wide_sh, wide_sh ? pl.grid_sh_w : pl.grid_sh, sB, c->S, Wb, B.sp_sh, c->prm.lds_nodes != 0);
+    const ShadowVariant vh = select_shadow(pl.stats, wide_sh, top, has_top);
+    KHPCHK(launch_variant<ShadowK>(SHADOW_TABLE, vh, wide_sh ? pl.grid_sh_w : pl.grid_sh, TRAV_BLOCK, shadow_lds(vh), sB,
+                                   c->S, Wb, B.sp_sh));
     timed(c, f, T_SHADOW, false, sB);
     timed(c, f, T_SHADOW_FINISH, true, sB);   // shadow stage = any-hit traversal + finish
-    if (pl.bdm) hipLaunchKernelGGL(k_shadow_finish<true>, dim3(c->grid_fin), dim3(256), 0, sB, c->S, Wb, cur ^ 1);
-    else hipLaunchKernelGGL(k_shadow_finish<false>, dim3(c->grid_fin), dim3(256), 0, sB, c->S, Wb, cur ^ 1);
+    KHPCHK(launch_variant<ShadowFinishK>(SHADOW_FINISH_TABLE, select_shadow_finish(pl.bdm), c->grid_fin, 256, 0, sB, c->S,
+                                         Wb, cur ^ 1));
     timed(c, f, T_SHADOW_FINISH, false, sB);
     if (sB != sA) HIPCHK(mark_stream(f, sB, k.done_b));
     if (pl.stats) {
@@ -4645,17 +4537,17 @@ static khp_status enqueue_chunk(khp_ctx* c, const BatchPlan& pl, const khp_rende
         HIPCHK(hipMemsetAsync(reinterpret_cast<char*>(Wv.cnt) + offsetof(Counters, fetch_ext), 0,
                               sizeof(Counters::fetch_ext), sA));
         timed(c, f, T_OTHER, true, sA);
-        launch_path(c->S.textured != 0, pl.path_wide, pl.fur_only, pl.lobes_on, pl.hair, pl.grid_path, sA, c->S, Wv, B.sp_path,
-                    B.PL, B.AH);
+        KHPCHK(launch_variant<PathK>(PATH_TABLE, select_path(pl.vf, pl.path_wide, B.AH.on != 0, false), pl.grid_path,
+                                     TRAV_BLOCK, PATH_LDS, sA, c->S, Wv, B.sp_path, B.PL, B.AH));
         HIPCHK(hipGetLastError());
         if (pl.ahead) ahead_commit(c, p, pl.call_paths);
         timed(c, f, T_OTHER, false, sA);
     }
     timed(c, f, T_OTHER, true, sA);
     if (!pl.use_path && Wv.cam0) hipLaunchKernelGGL(k_start, dim3(1), dim3(1), 0, sA, Wv.cnt, npaths);
-    else if (!pl.use_path && c->S.lens.radius > 0.0f)   // khp_set_lens: the lens twin
-        hipLaunchKernelGGL(k_generate<true>, dim3((npaths + 255) / 256), dim3(256), 0, sA, c->S, Wv);
-    else if (!pl.use_path) hipLaunchKernelGGL(k_generate<false>, dim3((npaths + 255) / 256), dim3(256), 0, sA, c->S, Wv);
+    else if (!pl.use_path)
+        KHPCHK(launch_variant<GenerateK>(GENERATE_TABLE, select_generate(pl.vf), (int)((npaths + 255) / 256), 256, 0, sA,
+                                         c->S, Wv));
     if (pl.bdm) {  // the light subpaths of this chunk's sample slots (frames x samples)
         const uint32_t nsub = pl.nf * ns * c->bd.light_paths * (uint32_t)c->S.n_lights;
         hipLaunchKernelGGL(k_light_paths, dim3((nsub + 63) / 64), dim3(64), 0, sA, c->S, Wv);
@@ -4671,10 +4563,12 @@ static khp_status enqueue_chunk(khp_ctx* c, const BatchPlan& pl, const khp_rende
         HIPCHK(hipMemsetAsync(Wi.shq, 0, sizeof(ShadowQ), sA));
         hipLaunchKernelGGL(k_img_connect, dim3((npaths + 255) / 256), dim3(256), 0, sA, c->S, Wi);
         timed(c, f, T_SHADOW, true, sA);
-        launch_shadow(pl.stats, false, pl.grid_sh, sA, c->S, Wi, B.sp_sh);
+        const ShadowVariant vh = select_shadow(pl.stats, false, false, false);
+        KHPCHK(launch_variant<ShadowK>(SHADOW_TABLE, vh, pl.grid_sh, TRAV_BLOCK, shadow_lds(vh), sA, c->S, Wi, B.sp_sh));
         timed(c, f, T_SHADOW, false, sA);
         timed(c, f, T_SHADOW_FINISH, true, sA);
-        hipLaunchKernelGGL(k_shadow_finish<true>, dim3(c->grid_fin), dim3(256), 0, sA, c->S, Wi, 0);
+        KHPCHK(launch_variant<ShadowFinishK>(SHADOW_FINISH_TABLE, select_shadow_finish(true), c->grid_fin, 256, 0, sA,
+                                             c->S, Wi, 0));
         timed(c, f, T_SHADOW_FINISH, false, sA);
     }
     BounceCarry k;
@@ -4691,8 +4585,8 @@ static khp_status enqueue_chunk(khp_ctx* c, const BatchPlan& pl, const khp_rende
         if (!k.prepped) hipLaunchKernelGGL(k_prep, dim3(1), dim3(1), 0, sA, Wv.cnt, w.shqb.as<ShadowQ>() + cur, cur);
         c->cur_bounce = (int)pl.hyb_from;
         timed(c, f, T_OTHER, true, sA);
-        launch_path(c->S.textured != 0, pl.hyb_wide, pl.fur_only, pl.lobes_on, pl.hair, pl.grid_path, sA, c->S, Wq, B.sp_path,
-                    B.PL, Ahead{}, true);
+        KHPCHK(launch_variant<PathK>(PATH_TABLE, select_path(pl.vf, pl.hyb_wide, false, true), pl.grid_path, TRAV_BLOCK,
+                                     PATH_LDS, sA, c->S, Wq, B.sp_path, B.PL, Ahead{}));
         HIPCHK(hipGetLastError());
         timed(c, f, T_OTHER, false, sA);
     }
@@ -5488,14 +5382,18 @@ static khp_status trace_persistent_run(khp_ctx* c, uint32_t n, const float* orig
     if (shadow) {
         SpillArea sp{w.spill_sh.as<int4>(), (uint32_t)c->grid_sh * TRAV_BLOCK};
         const bool wide = c->S.wide != nullptr && c->prm.wide_from == 0;  // the two-level any-hit loop ray by ray
-        launch_shadow(!prod, wide, wide ? c->grid_sh_w : c->grid_sh, c->stream, c->S, Wv, sp);
+        const ShadowVariant vh = select_shadow(!prod, wide, false, false);
+        KHPCHK(launch_variant<ShadowK>(SHADOW_TABLE, vh, wide ? c->grid_sh_w : c->grid_sh, TRAV_BLOCK, shadow_lds(vh),
+                                       c->stream, c->S, Wv, sp));
         (void)hipEventRecord(e1, c->stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(hit_out, Wv.vis, n, hipMemcpyDeviceToHost, c->stream));
     } else {
         SpillArea sp{w.spill.as<int4>(), (uint32_t)c->grid_ext_max * TRAV_BLOCK};
         const bool wide = c->S.wide != nullptr && c->prm.wide_from == 0;  // the two-level loop ray by ray
-        launch_extend(!prod, false, wide, wide ? c->grid_ext_w : c->grid_ext, c->stream, c->S, Wv, 0, sp);
+        const ExtendVariant ve = select_extend(variant_facts(c), !prod, false, wide, false, false);
+        KHPCHK(launch_variant<ExtendK>(EXTEND_TABLE, ve, wide ? c->grid_ext_w : c->grid_ext, TRAV_BLOCK, extend_lds(ve),
+                                       c->stream, c->S, Wv, 0, sp));
         (void)hipEventRecord(e1, c->stream);
         HIPCHK(t.ensure(4 * (size_t)n));
         HIPCHK(ob.ensure(4 * (size_t)n));

@@ -359,6 +359,21 @@ class RefitInfo(ctypes.Structure):
                 "root_box": np.array(self.root_box[:], np.float32)}
 
 
+class VariantFacts(ctypes.Structure):
+    """khp_variant_facts: what a render kernel's compile-time instance is chosen from (flags, but bounce)."""
+    _fields_ = [(k, c_uint32) for k in ("textured", "fur_only", "lobes_on", "hair", "env", "lens_on", "bd", "bounce",
+                                        "cam0", "stats", "cam", "wide", "top", "has_top", "ahead", "queue_start")]
+
+
+# khp_kernel_family (include/kirk_hip.h), in enum order: the kernel, and its template arguments in declaration order
+KERNEL_FAMILIES = (("k_path", ("tex", "wide", "kinds", "ra", "qs", "lens", "env")),
+                   ("k_shade", ("tex", "bd", "kinds", "lens", "env")),
+                   ("k_extend", ("stats", "cam", "wide", "top", "lens")),
+                   ("k_shadow", ("stats", "wide", "top")),
+                   ("k_aov_trace", ("tex", "lens")),
+                   ("k_generate", ("lens",)),
+                   ("k_shadow_finish", ("bd",)))
+
 # every symbol the header declares (checked by tests/test_abi.py)
 EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "khp_set_scene", "khp_build_accel",
             "khp_render", "khp_read_framebuffer", "khp_trace_closest", "khp_trace_any", "khp_get_stats",
@@ -386,7 +401,8 @@ EXPORTED = ["khp_create", "khp_destroy", "khp_last_error", "khp_abi_version", "k
             "khp_hair_eval_host", "khp_hair_sample_host", "khp_env_light_defaults", "khp_set_env_light",
             "khp_get_env_light", "khp_env_light_tables_host", "khp_env_light_sample_host", "khp_env_light_eval_host",
             "khp_debug_env_light_tables", "khp_debug_env_light", "khp_kmath_host", "khp_debug_kmath",
-            "khp_update_geometry", "khp_update_geometry_device", "khp_get_refit_info", "khp_refit_host"]
+            "khp_update_geometry", "khp_update_geometry_device", "khp_get_refit_info", "khp_refit_host",
+            "khp_kernel_variant_host", "khp_kernel_variant_table"]
 
 # khp_kmath_op (include/kirk_hip.h): the ops of khp_kmath_host / khp_debug_kmath, in enum order
 KMATH_OPS = ("mul", "add", "div", "sqrt", "rsqrt", "muladd", "floor", "f2i", "f2u", "i2f", "u2f", "u642f", "d2i2d",
@@ -568,6 +584,8 @@ def load_library(path: str | None = None) -> ctypes.CDLL:
         "khp_get_refit_info": (c_int, [c_void_p, P(RefitInfo)]),
         "khp_refit_host": (c_int, [P(SceneDesc), c_uint32, P(c_int32), P(c_int32), P(c_int32), P(c_float),
                                    P(c_float), P(c_float), P(ctypes.c_double)]),
+        "khp_kernel_variant_host": (c_int, [c_uint32, P(VariantFacts), P(c_uint32), P(c_uint32), P(c_uint32)]),
+        "khp_kernel_variant_table": (c_int, [c_uint32, c_uint32, P(c_uint32), P(c_uint32)]),
     }
     lib.khp_abi_version.restype = c_int
     lib.khp_abi_version.argtypes = []
@@ -605,6 +623,26 @@ def tonemap_log_sum(terms: np.ndarray, start: float = 0.0) -> np.float32:
     check(lib, lib.khp_tonemap_log_sum(t.ctypes.data_as(POINTER(ctypes.c_double)), t.size, float(start),
                                        ctypes.byref(out)), "khp_tonemap_log_sum")
     return np.float32(out.value)
+
+
+def kernel_variant(family: int, **facts) -> tuple:
+    """khp_kernel_variant_host (host only): (the instance's template arguments, grid_kind) for the
+    khp_variant_facts fields given (the others 0)."""
+    lib = load_library()
+    args, n, gk = (c_uint32 * 7)(), c_uint32(), c_uint32()
+    f = VariantFacts(**{k: int(v) for k, v in facts.items()})
+    check(lib, lib.khp_kernel_variant_host(family, ctypes.byref(f), args, ctypes.byref(n), ctypes.byref(gk)),
+          "khp_kernel_variant_host")
+    return tuple(args[:n.value]), gk.value
+
+
+def kernel_variant_table(family: int) -> list:
+    """khp_kernel_variant_table (host only): every compiled instance of the family, in table order."""
+    lib = load_library()
+    args, n, rows = (c_uint32 * 7)(), c_uint32(), []
+    while lib.khp_kernel_variant_table(family, len(rows), args, ctypes.byref(n)) == KHP_OK:
+        rows.append(tuple(args[:n.value]))
+    return rows
 
 
 def host_build(scene) -> dict:

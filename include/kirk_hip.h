@@ -1466,6 +1466,57 @@ khp_status khp_refit_host(const khp_scene* moved, uint32_t n_nodes, const int32_
                           const int32_t* node_count, const int32_t* object_ids,
                           float* node_boxes, float* obj_bounds, float* records, double* sah_cost);
 
+/* Which compile-time instance of a render kernel a launch takes (still ABI 17: symbols
+ * only; csrc/variant.h).  No device and no context: the renderer's own
+ * selectors and tables, for tests and tools.  An instance is returned as its template
+ * arguments in declaration order, defaults filled in, a bool as 0 / 1:
+ *   KHP_KERNEL_PATH          tex, wide, kinds, ra, qs, lens, env
+ *   KHP_KERNEL_SHADE         tex, bd, kinds, lens, env
+ *   KHP_KERNEL_EXTEND        stats, cam, wide, top, lens
+ *   KHP_KERNEL_SHADOW        stats, wide, top
+ *   KHP_KERNEL_AOV_TRACE     tex, lens
+ *   KHP_KERNEL_GENERATE      lens
+ *   KHP_KERNEL_SHADOW_FINISH bd
+ * args holds at least 7 words; n_args receives the count. */
+typedef enum {
+    KHP_KERNEL_PATH = 0,
+    KHP_KERNEL_SHADE = 1,
+    KHP_KERNEL_EXTEND = 2,
+    KHP_KERNEL_SHADOW = 3,
+    KHP_KERNEL_AOV_TRACE = 4,
+    KHP_KERNEL_GENERATE = 5,
+    KHP_KERNEL_SHADOW_FINISH = 6,
+    KHP_KERNEL_COUNT = 7
+} khp_kernel_family;
+/* Flags (0 / nonzero), but `bounce`.  The first seven are a batch's facts; the others are
+ * the inputs of one launch, each read by the families named. */
+typedef struct {
+    uint32_t textured;     /* the scene has textured materials or an environment map        */
+    uint32_t fur_only;     /* its materials use Lambert reflection and Marschner hair only   */
+    uint32_t lobes_on;     /* khp_set_hair_lobes: a lobe set other than R                    */
+    uint32_t hair;         /* a KHP_BSDF_CHIANG_HAIR material                                */
+    uint32_t env;          /* khp_set_env_light: the light is on                             */
+    uint32_t lens_on;      /* khp_set_lens: radius > 0                                       */
+    uint32_t bd;           /* khp_set_bdpt: the light-path variant runs                      */
+    uint32_t bounce;       /* shade: the bounce shaded                                       */
+    uint32_t cam0;         /* shade: bounce 0 recomputes its camera rays                     */
+    uint32_t stats;        /* extend, shadow: an instrumented render                         */
+    uint32_t cam;          /* extend: the launch makes its camera rays in place              */
+    uint32_t wide;         /* path, extend, shadow: on the two-level records                 */
+    uint32_t top;          /* extend, shadow: khp_ctx_params.lds_nodes                       */
+    uint32_t has_top;      /* extend, shadow: the tree has top records                       */
+    uint32_t ahead;        /* path: render-ahead is on                                       */
+    uint32_t queue_start;  /* path: the launch starts from a bounce's queue (path_from)      */
+} khp_variant_facts;
+/* The instance launched for `facts`, whether or not a setter would refuse the combination.
+ * grid_kind (nullable) receives 1 where a shade launch takes the light-path instances' grid,
+ * else 0.  KHP_EINVAL: a null argument, an unknown family. */
+khp_status khp_kernel_variant_host(uint32_t kernel, const khp_variant_facts* facts, uint32_t* args,
+                                   uint32_t* n_args, uint32_t* grid_kind);
+/* Row `index` of the family's table of compiled instances.  KHP_EINVAL: a null argument,
+ * an unknown family, an index past the table's end. */
+khp_status khp_kernel_variant_table(uint32_t kernel, uint32_t index, uint32_t* args, uint32_t* n_args);
+
 /* Fur fibers -> cone frusta exactly as CPU_Scene::flattenNode does with
  * m_fiberAsCylinder (CPU_Scene.cpp:121-144): base pulled back by 0.8 % of the
  * segment, base radius shrunk 5 % (segment index <= 3) or 10 %.
